@@ -21,7 +21,16 @@ cut pair; the line also times whole pairs per rank ("pairs") and the same split 
 boundary moved half a pair ("windows_split": N - 1 cut pairs, both exchanges per step).
 Barrier + synchronize around the K timed steps, max elapsed over ranks.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it makes and uploads the batch, warms up,
+times the K steps (the roofline kernels' launches of those steps carry their HIP events, so the
+roofline of the timed launches is in the line) and prints the result line.  --dump-outputs DIR
+then writes what the last timed step returned (dump_outputs).  --full adds every side leg, each
+with runs of its own: device idle, the single-call step, the entry-point timers, the isolated
+kernels, the upload-included rates, the hop-64 IBI pass, configs 2 and 5, spectral.analyze, the
+resampler, the N > 1 side modes and the CPU baseline (the --no-* options switch single legs of a
+--full run off).
 """
 from __future__ import annotations
 
@@ -171,7 +180,46 @@ def cpu_baseline(seconds, base_seed, workers):
             "tempo_ratio": rows[0][3], "pitch_ratio": rows[0][4]}
 
 
-def main():
+DUMP_DETAIL = ("energy_src", "energy_nc", "src_tempos", "nc_tempos", "nc_start_bpm", "tempo_margin_src",
+               "tempo_margin_nc", "chunk_lags", "chunk_lag_margin", "tuning", "tuning_margin", "chroma")
+
+
+def _save_finite(d, name, a, skip_if_absent=False):
+    """DIR/<name>.npy with finite values only.  Entries that are None / NaN / inf in `a` are written
+    as 0.0 and marked in <name>_missing.npy (1 NaN or None, 2 +inf, 3 -inf), which exists only then;
+    skip_if_absent: nothing is written when every entry is None / NaN (a figure this path does not
+    compute)."""
+    a = np.asarray(a, np.float64)
+    code = np.where(np.isnan(a), 1.0, np.where(np.isposinf(a), 2.0, np.where(np.isneginf(a), 3.0, 0.0)))
+    if skip_if_absent and a.size and (code == 1.0).all():
+        return
+    np.save(d / f"{name}.npy", np.where(code > 0, 0.0, a))
+    if code.any():
+        np.save(d / f"{name}_missing.npy", code)
+
+
+def dump_outputs(dirname, outcomes):
+    """What a caller of the timed path received for the last timed step, as DIR/<name>.npy (f64,
+    every value finite: _save_finite): `result_<field>`, one value per pair of the batch for every
+    sharded.RES_FIELDS figure the path computes (ok flag, ratios, CIs, counts, durations, median
+    tempos; a field that is None in every pair, such as the IBI ratio of a step without the IBI
+    pass, has no file), and every per-window / per-chunk array of the outcomes' detail
+    (DUMP_DETAIL) concatenated over the pairs in batch order, with `<name>_count` the entries each
+    pair contributed.  A 64-pair batch dumps well under 1 MB."""
+    from nightcore_analyzer.sharded import RES_FIELDS, result_row
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    rows = np.array([result_row(o) for o in outcomes], np.float64).reshape(len(outcomes), len(RES_FIELDS))
+    for c, field in enumerate(RES_FIELDS):
+        _save_finite(d, f"result_{field}", rows[:, c], skip_if_absent=field != "ok")
+    for name in DUMP_DETAIL:
+        parts = [np.asarray(o.detail[name], np.float64).reshape(-1) if o.detail.get(name) is not None
+                 else np.zeros(0) for o in outcomes]
+        _save_finite(d, name, np.concatenate(parts) if parts else np.zeros(0))
+        np.save(d / f"{name}_count.npy", np.array([len(p) for p in parts], np.float64))
+
+
+def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
@@ -193,8 +241,17 @@ def main():
                          "nightcore_analyzer.sharded, BASELINE config 4), or whole pairs per rank; the other mode "
                          "and the split-boundary variant are timed beside the headline")
     ap.add_argument("--workers", type=int, default=min(16, os.cpu_count() or 1))
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side leg (device idle, single-call step, entry-point "
+                         "timers, isolated kernels, upload-included, IBI pass, configs 2 and 5, spectral, resample, "
+                         "N > 1 side modes, CPU baseline); a plain run times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64; see dump_outputs)")
+    return ap.parse_args()
 
+
+def main():
+    args = parse_args()
     import torch
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -288,7 +345,7 @@ def main():
         # 10.2-10.3 ms per step where the next ones ran 9.5-9.7 (profiles/r4_bench_timing_variants.txt)
         eng.analyze_batches([own] * max(2, args.steps), params)
     if win_mode:   # warmed at the timed size, as the pipelined call above
-        for off in (0.0, 0.5):
+        for off in ((0.0, 0.5) if args.full else (0.0,)):   # 0.5: the windows_split side mode of --full
             run_windows(max(1, args.warmup, args.steps), off)
 
     # timed region: K steps with every launch of the roofline kernels (stft_mel, cqt_low,
@@ -298,7 +355,7 @@ def main():
     # kernel's stream, what rocprofv3 --kernel-trace reports, waiting for CUs the other stream
     # holds included).  No other kernel is timed in the region: events around every launch cost
     # the step ~5 %, the kernels' own execution spans ~3 % (profiles/r4_timer_modes_probe.txt);
-    # every kernel's time alone is in roofline.isolated
+    # every kernel's time alone is in roofline.isolated (--full)
     eng.kernel_profile(4)
     barrier()
     torch.cuda.synchronize()
@@ -315,6 +372,7 @@ def main():
     # one analyze_sharded call of K steps (its interior groups pipelined the same way)
     pipelined = not args.no_pipeline
     gather_rebuild = None
+    last = None                                 # the last timed step's outcomes (--dump-outputs)
     t0 = time.perf_counter()
     if win_mode:
         res = run_windows(args.steps)
@@ -326,7 +384,7 @@ def main():
         res = eng.analyze_batches([own] * args.steps, params)
     else:
         for _ in range(args.steps):
-            step()
+            last = step()
     torch.cuda.synchronize()
     barrier()
     el = time.perf_counter() - t0
@@ -357,6 +415,8 @@ def main():
         if any(not np.array_equal(tabs[0][b], np.array(result_row(o), np.float64), equal_nan=True)
                for b, o in enumerate(mine)):
             raise RuntimeError("a gathered result row differs from its rebuilt outcome")
+        if args.dump_outputs and rank == 0:
+            last = list(res[-1])                # every pair's outcome of the last step, rebuilt here
         del res, mine, tabs                     # not kept (see below)
     elif pipelined:
         if len(res) != args.steps or any(len(r) != len(outs) for r in res):
@@ -365,42 +425,51 @@ def main():
             raise RuntimeError("a pipelined batch differs from the single-call result")
         # the checked outcomes (K x 64 pairs) are not kept: holding them slowed the side legs
         # measured after (spectral.analyze 5.0 -> 9.9 ms per call; profiles/r4_bench_timing_variants.txt)
+        if args.dump_outputs:
+            last = res[-1]
         del res
     evt = eng.kernel_times()
     spans = eng.kernel_spans()
     eng.kernel_profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    del last
+    full = args.full                            # the side legs below: --full only
+    el = max_over_ranks(el)
+    step_ms = el / args.steps * 1e3
+    value = (win_total if win_mode else world * win_per_step) * args.steps / el
 
     # device idle, untraced: extra steps of the same call with every kernel recording its own
     # execution span (profile mode 2, ~3 % slower than the timed steps), then 1 - the union of the
     # spans over their extent (nc_profile_read_busy).  The extent starts at the call's first
     # kernel, so the call's start-up (first trim read-back, first group plan) is in it
-    n_idle = max(2, min(args.steps, 10))
-    eng.kernel_profile(2)
-    barrier()
-    torch.cuda.synchronize()
-    if win_mode:
-        run_windows(n_idle)
-    elif pipelined:
-        eng.analyze_batches([own] * n_idle, params)
-    else:
-        for _ in range(n_idle):
-            step()
-    busy_ms, extent_ms, idle_launches = eng.device_busy()
-    eng.kernel_profile(False)
-    idle_frac = max_over_ranks(1.0 - busy_ms / extent_ms) if extent_ms > 0 else None
-    device_idle = {"frac": idle_frac, "busy_ms": busy_ms, "extent_ms": extent_ms, "steps": n_idle,
-                   "launches": idle_launches,
-                   "how": "untimed steps of the headline call, the execution spans of the engine's timed kernels "
-                          "recorded (stft_mel, window_tg, tuning_peaks, decimate, tuning_select, cqt_low, cqt_high, "
-                          "tempo_beat, trim_blocks; the small unspanned kernels count as idle, so this is an upper "
-                          "bound): 1 - union of spans / first start..last end (nc_profile_read_busy); max over ranks"}
-    el = max_over_ranks(el)
-    step_ms = el / args.steps * 1e3
-    value = (win_total if win_mode else world * win_per_step) * args.steps / el
+    idle_frac = device_idle = None
+    if full:
+        n_idle = max(2, min(args.steps, 10))
+        eng.kernel_profile(2)
+        barrier()
+        torch.cuda.synchronize()
+        if win_mode:
+            run_windows(n_idle)
+        elif pipelined:
+            eng.analyze_batches([own] * n_idle, params)
+        else:
+            for _ in range(n_idle):
+                step()
+        busy_ms, extent_ms, idle_launches = eng.device_busy()
+        eng.kernel_profile(False)
+        idle_frac = max_over_ranks(1.0 - busy_ms / extent_ms) if extent_ms > 0 else None
+        device_idle = {"frac": idle_frac, "busy_ms": busy_ms, "extent_ms": extent_ms, "steps": n_idle,
+                       "launches": idle_launches,
+                       "how": "untimed steps of the headline call, the execution spans of the engine's timed kernels "
+                              "recorded (stft_mel, window_tg, tuning_peaks, decimate, tuning_select, cqt_low, "
+                              "cqt_high, tempo_beat, trim_blocks; the small unspanned kernels count as idle, so this "
+                              "is an upper bound): 1 - union of spans / first start..last end "
+                              "(nc_profile_read_busy); max over ranks"}
 
     # N > 1: the other modes beside the headline, K steps each, same clock
     modes = None
-    if world > 1:
+    if world > 1 and full:
         modes = {}
         # windows_nogather: the headline's steps without the final outcome all-gather (each rank
         # keeps the outcomes of the pairs it owns)
@@ -454,7 +523,7 @@ def main():
 
     # the same steps as separate analyze calls (each with its own start-up), for comparison
     single_ms = None
-    if pipelined:
+    if pipelined and full:
         torch.cuda.synchronize()
         ts = time.perf_counter()
         nsc = max(1, min(args.steps, 5))
@@ -464,12 +533,14 @@ def main():
         single_ms = (time.perf_counter() - ts) / nsc * 1e3
 
     # entry-point HIP-event timers (separate, untimed steps)
-    eng.start_timers()
-    ksteps = max(1, min(args.steps, 3))
-    for _ in range(ksteps):
-        step()
-    timers = eng.stop_timers()
-    per = {k: (ms / n, n // ksteps) for k, (ms, n) in timers.items()}
+    per = None
+    if full:
+        eng.start_timers()
+        ksteps = max(1, min(args.steps, 3))
+        for _ in range(ksteps):
+            step()
+        timers = eng.stop_timers()
+        per = {k: (ms / n, n // ksteps) for k, (ms, n) in timers.items()}
 
     # algorithmic bytes / flops per launch = SURVEY.md §8d per-unit figure x units per launch
     units = {"stft_mel": (win_per_step, WIN_BYTES, WIN_FLOP),
@@ -529,22 +600,25 @@ def main():
         roofline["window_tg"] = roof("window_tg", kper, wtg_units, span=kspan)
     # the same kernels launched alone (streams serialized for one more untimed step): their own
     # speed, where the timed launches share the chip with the other streams' chains
-    eng.set_serial(True)
-    eng.kernel_profile(1)
-    step()
-    iso = eng.kernel_times()
-    eng.kernel_spans()
-    eng.kernel_profile(False)
-    eng.set_serial(False)
-    iso_t = {k: (ms / n, n) for k, (ms, n) in iso.items()}
-    roofline["isolated"] = {"kernels_ms_per_step": {k: round(v[0], 4) for k, v in iso.items()},
-                            **{k: roof(k, iso_t) for k in units if k in iso_t},
-                            **({"window_tg": roof("window_tg", iso_t, wtg_units)} if "window_tg" in iso_t else {})}
+    iso = {}
+    if full:
+        eng.set_serial(True)
+        eng.kernel_profile(1)
+        step()
+        iso = eng.kernel_times()
+        eng.kernel_spans()
+        eng.kernel_profile(False)
+        eng.set_serial(False)
+        iso_t = {k: (ms / n, n) for k, (ms, n) in iso.items()}
+        roofline["isolated"] = {"kernels_ms_per_step": {k: round(v[0], 4) for k, v in iso.items()},
+                                **{k: roof(k, iso_t) for k in units if k in iso_t},
+                                **({"window_tg": roof("window_tg", iso_t, wtg_units)} if "window_tg" in iso_t
+                                   else {})}
 
     # upload included: the same K steps with every step's 64 pairs copied host -> HBM from
     # pinned memory on a copy stream, double-buffered (step j + 1 uploads while step j runs)
     upl = None
-    if not args.no_upload and world == 1:
+    if full and not args.no_upload and world == 1:
         host = signals.buf.cpu().pin_memory()
         bufs = [signals.buf, torch.empty_like(signals.buf)]
         cs = torch.cuda.Stream(eng.dev)
@@ -613,7 +687,7 @@ def main():
         del host16, raw, q16, bufs
 
     ibi = None
-    if not args.no_ibi and rank == 0:
+    if full and not args.no_ibi and rank == 0:
         sub = E.DeviceSignals(own.buf, own.off[:4], own.length[:4])
         eng.analyze(signals=sub, params=E.Params(compute_ibi=True))
         torch.cuda.synchronize()
@@ -632,7 +706,7 @@ def main():
     # BASELINE configs[1]: one 3-min pair, the whole run() with its defaults (hop-64 IBI pass
     # included), host arrays in: upload + analysis + result assembly, latency per call
     cfg2 = None
-    if not args.no_config5 and rank == 0 and world == 1:
+    if full and not args.no_config5 and rank == 0 and world == 1:
         nc2, src2 = pairs[own_ids[0]]
         for _ in range(2):
             eng.analyze(signals=eng.upload_signals([nc2, src2]), params=E.Params())
@@ -653,7 +727,7 @@ def main():
     # BASELINE configs[4]: one 60-min pair, the whole run() incl. the hop-64 IBI pass, plus the
     # waveform xcorr verification search (xcorr.estimate_speed_xcorr) over the same signals
     cfg5 = None
-    if not args.no_config5 and rank == 0 and world == 1:
+    if full and not args.no_config5 and rank == 0 and world == 1:
         from nightcore_analyzer import xcorr as X
         from nightcore_analyzer import synth
         nc5, src5 = synth.make_pair(3600.0, 5000)          # in-process: no fork after GPU init
@@ -677,7 +751,7 @@ def main():
     # spectral.analyze statistics of every resident file of the batch in one
     # call (spectral.py:52-94); per-kernel HIP events on the launch stream, the oracle beside it
     spec = None
-    if not args.no_spectral and rank == 0:
+    if full and not args.no_spectral and rank == 0:
         srs = [22050] * own.n_files
         ev, h, keep = eng.spectral_frames(own.buf, own.off, own.length, srs)
         ev.synchronize()
@@ -725,7 +799,7 @@ def main():
     # the load-time resampler (io.py:54) on 44.1 kHz copies of the batch's
     # src files, resident in HBM (nc_resample_poly, bit-identical to scipy.signal.resample_poly)
     rsmp = None
-    if not args.no_resample and rank == 0:
+    if full and not args.no_resample and rank == 0:
         import scipy.signal
         from nightcore_analyzer.ops import poly_plan
         n_files = min(16, len(own_ids))
@@ -811,8 +885,10 @@ def main():
                 "isolated_step": sorted(set(iso) - set(kstep)),
                 "how": "the roofline kernels: HIP events around their launches in the timed steps (sharing the "
                        "chip with the other streams); every other kernel: HIP events in one more step with the "
-                       "streams serialized (roofline.isolated)"},
-            "entry_points_ms_per_step": {k: round(v[0] * v[1], 4) for k, v in per.items()},
+                       "streams serialized (roofline.isolated, --full only)"},
+            "entry_points_ms_per_step": {k: round(v[0] * v[1], 4) for k, v in per.items()} if per is not None else None,
+            # False: a plain run, the side legs (device idle, isolated kernels, entry points, ...) not run
+            "full": full,
             "check": {"tempo_ratio_pair0": tr, "pitch_ratio_pair0": pr},
             "build": prov,
         }
@@ -834,7 +910,7 @@ def main():
             line["spectral"] = spec
         if rsmp is not None:
             line["resample"] = rsmp
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.seconds, 1000, args.cpu_workers or host_cores())
         print(json.dumps(line), flush=True)
     if world > 1:

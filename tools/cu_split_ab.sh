@@ -16,7 +16,7 @@ for r in $(seq 1 $ROUNDS); do
       k=${spec%%:*}
       env_="NC_CU_SPLIT=$spec NC_STFT_CUS=$k NC_CHROMA_CUS=$((256 - k))"
     fi
-    env $env_ timeout -k 10 300 python3 -u bench.py --steps 20 --no-cpu-baseline --no-ibi --no-config5 --no-spectral \
+    env $env_ timeout -k 10 300 python3 -u bench.py --full --steps 20 --no-cpu-baseline --no-ibi --no-config5 --no-spectral \
       --no-resample --no-upload > $O/b_${spec/:/_}_$r.json 2> $O/b_${spec/:/_}_$r.err || { echo "bench $spec failed"; tail -5 $O/b_${spec/:/_}_$r.err; exit 1; }
     python3 -c "
 import json; d=json.load(open('$O/b_${spec/:/_}_$r.json')); k=d['kernels_ms_per_step']

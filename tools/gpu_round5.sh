@@ -22,7 +22,7 @@ bash tools/pmc_passes.sh $O/issue windows chroma > $O/issue.log 2>&1 || { echo "
 python3 tools/pmc_report.py $O/issue/windows/stats $O/issue/windows/p1 $O/issue/windows/p2 $O/issue/windows/p3 \
   $O/issue/chroma/stats $O/issue/chroma/p1 $O/issue/chroma/p2 $O/issue/chroma/p3 > $O/issue_report.body 2>&1
 { echo "# build: $(python3 -c 'import json, bench; print(json.dumps(bench.build_provenance()))')"; cat $O/issue_report.body; } > $O/issue_report.txt
-timeout -k 10 500 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 500 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
 cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $R/$O/prof -o run --output-format csv -- \
   python3 $R/bench.py --no-cpu-baseline > $R/$O/prof_bench.json 2> $R/$O/prof.err || { echo "rocprof failed"; tail -20 $R/$O/prof.err; exit 1; }
 cd $R && python3 tools/rocprof_timed.py $O/prof/run_kernel_trace.csv $O/prof_bench.json $O/rocprof_timed.json

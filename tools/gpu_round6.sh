@@ -22,7 +22,7 @@ bash tools/pmc_traffic.sh $O/pmc r6_traffic.json profiles/r6_fetch_calibration.j
 python3 -c "
 import json; d=json.load(open('profiles/r6_traffic.json'))
 for k, v in d['kernels'].items(): print(k, v['hbm_bytes_per_launch'], v.get('alg_bytes_per_launch'), v.get('calibration'))"
-timeout -k 10 500 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 500 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
 cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $R/$O/prof -o run --output-format csv -- \
   python3 $R/bench.py --no-cpu-baseline > $R/$O/prof_bench.json 2> $R/$O/prof.err || { echo "rocprof failed"; tail -20 $R/$O/prof.err; exit 1; }
 cd $R && python3 tools/rocprof_timed.py $O/prof/run_kernel_trace.csv $O/prof_bench.json $O/rocprof_timed.json

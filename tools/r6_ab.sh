@@ -15,7 +15,7 @@ for r in $(seq 1 $ROUNDS); do
   for spec in $SPECS; do
     name=${spec%%:*}; vars=""
     [ "$name" != "$spec" ] && vars=${spec#*:} && vars=${vars//,/ }
-    env $vars timeout -k 10 300 python3 -u bench.py --steps 30 --no-cpu-baseline --no-ibi --no-config5 \
+    env $vars timeout -k 10 300 python3 -u bench.py --full --steps 30 --no-cpu-baseline --no-ibi --no-config5 \
       --no-spectral --no-resample --no-upload > $O/${name}_$r.json 2> $O/${name}_$r.err || { echo "bench $name failed"; tail -5 $O/${name}_$r.err; exit 1; }
     python3 -c "
 import json; d=json.load(open('$O/${name}_$r.json')); i=d['roofline']['isolated']['kernels_ms_per_step']

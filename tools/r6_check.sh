@@ -19,7 +19,7 @@ if ls tools/var/*/libncgpu.so > /dev/null 2>&1; then
   timeout -k 10 400 python3 -u tools/var_bench.py tools/var/*/libncgpu.so > $O/var_bench.txt 2>&1 || { echo "var bench failed"; tail -20 $O/var_bench.txt; exit 1; }
   cat $O/var_bench.txt
 fi
-timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
 python3 -c "
 import json; d=json.load(open('$O/bench.json')); r=d['roofline']
 print('value', round(d['value']), 'ms', round(d['ms_per_step'],3), 'dom', r['kernel'], round(r['avg_launch_ms'],4), round(r['frac'],4))

@@ -6,7 +6,7 @@ set -o pipefail
 O=$1; N=$2; shift 2
 mkdir -p $O
 NC_BENCH_REHEARSE=1 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-  --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --steps 5 --warmup 2 \
+  --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --full --gpus $N --steps 5 --warmup 2 \
   --no-cpu-baseline --no-config5 --no-spectral --no-resample --no-upload "$@" > $O/n$N.json 2> $O/n$N.err \
   || { echo "rehearsal N=$N failed"; tail -20 $O/n$N.err; exit 1; }
 python3 -c "
