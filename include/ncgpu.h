@@ -409,6 +409,39 @@ int nc_resample_poly(nc_ctx* ctx, const float* x, const int64_t* in_off, const i
 int nc_pcm16_to_f32(nc_ctx* ctx, const int16_t* x, int64_t n, float* y, void* stream);
 
 /* -------------------------------------------------------------------------
+ * R2  speed render — replaces the `sox SRC DST speed F` the reference's workflow
+ *     shells out to (workflow.py:108-118) with an arbitrary-ratio band-limited
+ *     resampler.  PARITY UNPINNED: sox is not installed and the reference holds no
+ *     resampler; the definition is this project's own:
+ *       Q = 1e6, Z = 32, BETA = 10.06, ROLL = 0.9, P = round(F Q), 0.25 <= F <= 4,
+ *       n_out = ceil(n Q / P), c = ROLL min(1, Q / P),
+ *       t_m = (m P div Q) + ((m P mod Q) / Q),
+ *       h(u) = c sinc(c u) I0(BETA sqrt(1 - (c u / Z)^2)) / I0(BETA), |c u| < Z,
+ *       y[m] = sum_j x[j] h(t_m - j), x zero outside [0, n).
+ *
+ * nc_speed_out_len (host only, no context): *p_out = P (nullable) and
+ *     n_out[f] = ceil(n_in[f] Q / P) for n_files host lengths; -2 when F is outside
+ *     [0.25, 4].  The renderer uses the same formula on the device.
+ * nc_speed_render: file f's y[out_off[f] + m], m < n_out(in_len[f]), and
+ *     peak[f] = max_m |y[m]| (0 for an empty file) in one launch; files of one call
+ *     share p = P.  in_off / in_len / out_off: device int64 [n_files] (samples);
+ *     max_out = the largest n_out; peak: device float [n_files].  The filter is
+ *     read from a 512-point-per-zero-crossing table by linear interpolation and
+ *     summed in f32: within 1e-5 max|x| of the definition.  No workspace, no host
+ *     synchronisation.
+ * nc_f32_to_pcm16: q[out_off[f] + i out_stride] = clamp(rint(x[in_off[f] + i] 32768),
+ *     -32768, 32767) (round half to even), i < in_len[f]; out_stride = channels
+ *     interleaves the channels of one WAV file; clipped[f] (device int) = samples
+ *     whose rounded value fell outside the 16-bit range.  max_len = largest in_len.
+ * ------------------------------------------------------------------------- */
+int nc_speed_out_len(double factor, const int64_t* n_in, int n_files, int64_t* p_out, int64_t* n_out);
+int nc_speed_render(nc_ctx* ctx, const float* x, const int64_t* in_off, const int64_t* in_len, int n_files,
+                    int64_t p, float* y, const int64_t* out_off, int64_t max_out, float* peak, void* stream);
+int nc_f32_to_pcm16(nc_ctx* ctx, const float* x, const int64_t* in_off, const int64_t* in_len, int n_files,
+                    int64_t max_len, int16_t* q, const int64_t* out_off, int64_t out_stride, int* clipped,
+                    void* stream);
+
+/* -------------------------------------------------------------------------
  * MELODIA front end (opt-in; replaces the frame-level part of essentia's
  * PredominantPitchMelodia that pitch.estimate_pitch_melodia calls,
  * pitch.py:210-215: frameSize 2048, hopSize 128).  PARITY UNPINNED: essentia is

@@ -98,6 +98,13 @@ int launch_resample_poly(const float* x, const int64_t* in_off, const int64_t* i
                          float* y, const int64_t* out_off, const int64_t* out_len, int64_t max_out,
                          const double* h, int h_len, int up, int down, int64_t pre_remove, hipStream_t st);
 
+int64_t speed_factor_p(double factor);
+int64_t speed_out_len_host(int64_t n, int64_t P);
+int launch_speed_render(Context& ctx, const float* x, const int64_t* in_off, const int64_t* in_len, int n_files,
+                        int64_t P, float* y, const int64_t* out_off, int64_t max_out, float* peak, hipStream_t st);
+int launch_f32_to_pcm16(const float* x, const int64_t* in_off, const int64_t* in_len, int n_files, int64_t max_len,
+                        int16_t* q, const int64_t* out_off, int64_t out_stride, int* clipped, hipStream_t st);
+
 int launch_energy_gate(const double* energy, const int* w0, const int* w1, int n_groups, double gate_db,
                        uint8_t* active, hipStream_t st);
 int launch_collect_valid(const double* bpm, const int* nbeats, const uint8_t* active, const int* w0, const int* w1,
@@ -573,6 +580,40 @@ int nc_pcm16_to_f32(nc_ctx* ctx, const int16_t* x, int64_t n, float* y, void* st
   CHECK_CTX(ctx);
   SET_DEVICE(ctx);
   return nc::launch_pcm16_to_f32(x, n, y, (hipStream_t)stream);
+}
+
+int nc_speed_out_len(double factor, const int64_t* n_in, int n_files, int64_t* p_out, int64_t* n_out) {
+  const int64_t P = nc::speed_factor_p(factor);
+  if (P < 0) {
+    nc::set_error("nc_speed_out_len: factor outside [0.25, 4]");
+    return -2;
+  }
+  if (p_out) *p_out = P;
+  for (int f = 0; f < n_files; ++f) {
+    if (n_in[f] < 0 || n_in[f] > (INT64_C(1) << 40)) {
+      nc::set_error("nc_speed_out_len: input length outside 0 .. 2^40");
+      return -2;
+    }
+    n_out[f] = nc::speed_out_len_host(n_in[f], P);
+  }
+  return 0;
+}
+
+int nc_speed_render(nc_ctx* ctx, const float* x, const int64_t* in_off, const int64_t* in_len, int n_files,
+                    int64_t p, float* y, const int64_t* out_off, int64_t max_out, float* peak, void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_speed_render(ctx->c, x, in_off, in_len, n_files, p, y, out_off, max_out, peak,
+                                 (hipStream_t)stream);
+}
+
+int nc_f32_to_pcm16(nc_ctx* ctx, const float* x, const int64_t* in_off, const int64_t* in_len, int n_files,
+                    int64_t max_len, int16_t* q, const int64_t* out_off, int64_t out_stride, int* clipped,
+                    void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_f32_to_pcm16(x, in_off, in_len, n_files, max_len, q, out_off, out_stride, clipped,
+                                 (hipStream_t)stream);
 }
 
 int nc_melodia_salience(nc_ctx* ctx, const float* sig, const int64_t* file_off, const int64_t* file_len,

@@ -60,6 +60,8 @@ struct Tables {
   uint4* cqm_b = nullptr;
   int* cqm_bexp = nullptr;      // [kNTunings][36] filter scale exponents
   float cqm_gpow[7] = {};       // bound of max|octave o| / max|octave 0|: (sqrt(2) sum|h|)^o, rounded up
+  // speed renderer (speed.hip): sinc(v) kaiser(v / 32; 10.06) at v = i / 512, i <= 32 * 512
+  float* speed_tab = nullptr;
 };
 
 struct KernelTimers;  // nc_prof.cpp
@@ -146,6 +148,9 @@ struct BootArgs {
 
 void build_tables(Context& ctx);
 void free_tables(Context& ctx);
+// speed.hip: the renderer's filter g on its table grid (f64 on the host, rounded to f32)
+int speed_table_len();
+void speed_table(float* tab);
 
 // error plumbing (thread-local message, int status)
 void set_error(const std::string& msg);

@@ -439,6 +439,12 @@ void build_tables(Context& ctx) {
     t.cqm_b = upload(frag);
     t.cqm_bexp = upload(bexp);
   }
+  // speed renderer's interpolation filter (speed.hip)
+  {
+    std::vector<float> g((size_t)speed_table_len());
+    speed_table(g.data());
+    t.speed_tab = upload(g);
+  }
   // octave bound: |y_{o+1}| <= sqrt(2) sum|h| max|y_o| (f32 accumulation adds < 1e-6
   // relative; the factor is rounded up by 1e-4 and the kernel keeps 3 bits of headroom)
   {
@@ -454,7 +460,7 @@ void free_tables(Context& ctx) {
   void* ptrs[] = {t.tw, t.hann2048, t.hann_ac512, t.hann_ac64, t.wsq512, t.wsq64, t.mel_lo,  t.mel_len, t.mel_off,
                   t.mel_w,  t.cqt_lo,   t.cqt_len,    t.cqt_off,  t.cqt_w,   t.cqt_inv_sqrt_len, t.halfband,
                   t.mel_w4, t.mel_lo4, t.mel_nj4, t.mel_band,
-                  t.cqm_b,   t.cqm_bexp};
+                  t.cqm_b,   t.cqm_bexp, t.speed_tab};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   t = Tables();

@@ -37,7 +37,28 @@ def _build_parser() -> argparse.ArgumentParser:
     p.add_argument("--auto-align", action="store_true", default=False,
                    help="Attempt automatic intro-offset detection (RMS envelope correlation)")
     p.add_argument("--quiet", "-q", action="store_true", help="Suppress progress output")
+    p.add_argument("--render-hqnc", metavar="OUT.wav", default=None,
+                   help="After the analysis, render the source sped up by the detected factor (IBI ratio, "
+                        "else tempo ratio) to this WAV file on the GPU")
+    p.add_argument("--refine", action="store_true",
+                   help="With --render-hqnc: re-analyse the render against the nightcore and correct the "
+                        "factor until the residual is inside tolerance before writing the file")
     return p
+
+
+def _render_hqnc(args, result, nc_path: Path, src_path: Path, log) -> None:
+    from . import render
+    factor = result.ibi_ratio if result.ibi_ratio is not None else result.tempo_ratio
+    if args.refine:
+        ref = render.refine_speed(str(nc_path), str(src_path), start=factor, log=log)
+        factor = ref.factor
+        if log is not None:
+            log(f"Refined speed factor: {factor:.6f}× after {ref.corrections} correction(s)"
+                + ("" if ref.converged else "  (not converged)"))
+    info = render.speed_file(src_path, args.render_hqnc, factor)
+    if log is not None:
+        log(f"\nHQNC written to: {info.path}  (speed {info.factor:.6f}×, peak {info.peak_dbfs:+.2f} dBFS, "
+            f"{info.clipped_samples} clipped samples)")
 
 
 def output_dict(result) -> dict:
@@ -68,6 +89,8 @@ def main(argv: list[str] | None = None) -> int:
         errors.append(f"Source file not found:    {src_path}")
     if args.hop >= args.window:
         errors.append("--hop must be less than --window for overlapping windows")
+    if args.refine and not args.render_hqnc:
+        errors.append("--refine needs --render-hqnc")
     if errors:
         for e in errors:
             print(f"ERROR: {e}", file=sys.stderr)
@@ -94,6 +117,12 @@ def main(argv: list[str] | None = None) -> int:
     if not args.quiet:
         print()
         print(result)
+    if args.render_hqnc:
+        try:
+            _render_hqnc(args, result, nc_path, src_path, log)
+        except Exception as exc:
+            print(f"\nERROR: {exc}", file=sys.stderr)
+            return 1
     return 0
 
 

@@ -713,7 +713,7 @@ class Engine:
     MAX_GROUPS_IN_FLIGHT = 5
 
     KERNEL_TAGS = ("stft_mel", "window_tg", "tuning_peaks", "decimate", "cqt_low", "cqt_high", "trim_blocks", "tempo_beat",
-                   "tg_slide", "spectral_frames", "spectral_bins")
+                   "tg_slide", "spectral_frames", "spectral_bins", "speed_render")
 
     def kernel_profile(self, on) -> None:
         """The library's per-kernel timers (nc_profile_enable): False/0 off, True/1 HIP events
@@ -773,8 +773,9 @@ class Engine:
     def upload_signals(self, arrays: Sequence[np.ndarray]) -> DeviceSignals:
         """The files into one f32 HBM buffer (64-sample aligned offsets).  When every file is
         16-bit PCM as stored (``io.Pcm16``) the 2-byte samples are uploaded and widened on the
-        device (``nc_pcm16_to_f32``, k / 32768 exactly): half the host -> HBM bytes."""
-        from .io import Pcm16, as_f32
+        device (``nc_pcm16_to_f32``, k / 32768 exactly): half the host -> HBM bytes.  A file
+        that is already in HBM (``io.DeviceAudio``, a render) is copied device to device."""
+        from .io import DeviceAudio, Pcm16, as_f32
         lens = np.array([len(a) for a in arrays], dtype=np.int64)
         offs = np.zeros(len(arrays), dtype=np.int64)
         tot = 0
@@ -784,10 +785,15 @@ class Engine:
         pcm = bool(arrays) and all(isinstance(a, Pcm16) for a in arrays)
         host = torch.zeros(max(_ALIGN, tot), dtype=torch.int16 if pcm else torch.float32, pin_memory=True)
         hv = host.numpy()
+        resident = [(a, int(o)) for a, o in zip(arrays, offs) if isinstance(a, DeviceAudio)]
         for a, o in zip(arrays, offs):
-            hv[o:o + len(a)] = a.view(np.ndarray) if pcm else as_f32(a)
+            if not isinstance(a, DeviceAudio):
+                hv[o:o + len(a)] = a.view(np.ndarray) if pcm else as_f32(a)
         if not pcm:
-            return DeviceSignals(host.to(self.dev, non_blocking=True), offs, lens)
+            buf = host.to(self.dev, non_blocking=True)
+            for a, o in resident:
+                buf[o:o + len(a)].copy_(a.tensor.to(torch.float32).reshape(-1), non_blocking=True)
+            return DeviceSignals(buf, offs, lens)
         raw = host.to(self.dev, non_blocking=True)
         buf = torch.empty(raw.numel(), dtype=torch.float32, device=self.dev)
         self.call("nc_pcm16_to_f32", raw.data_ptr(), raw.numel(), buf.data_ptr(), self.stream())

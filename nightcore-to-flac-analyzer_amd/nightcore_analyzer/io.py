@@ -11,6 +11,9 @@
 * ``slice_windows`` (io.py:82-112) returns views like the reference, with the
   window energies computed by ``nc_window_energy`` on the GPU.
 * ``energy_gate`` (io.py:115-126) is the same list filter.
+* ``read_wav_channels`` / ``write_wav`` (no counterpart in the reference's io.py, which leaves
+  this to soundfile and sox): the channel-preserving WAV read and the WAV writer behind
+  ``render.speed_file`` and ``loudness``; ``DeviceAudio`` is a signal that is already in HBM.
 """
 from __future__ import annotations
 
@@ -58,10 +61,27 @@ class Pcm16(np.ndarray):
         return self.view(np.ndarray).astype(np.float32) / np.float32(32768.0)
 
 
+class DeviceAudio:
+    """A mono float32 signal already resident in HBM (``ops.speed_render_device``'s output): the
+    engine's loaders (``pipeline.run``, ``Engine.upload_signals``) take it in place of a
+    decoded array and copy it device to device, without a trip through the host."""
+
+    def __init__(self, tensor, sr: int = SAMPLE_RATE):
+        self.tensor, self.sr = tensor, int(sr)
+
+    def __len__(self) -> int:
+        return int(self.tensor.numel())
+
+    def numpy(self) -> np.ndarray:
+        return self.tensor.cpu().numpy()
+
+
 def as_f32(a) -> np.ndarray:
     """The float32 samples of ``a``: a Pcm16 scaled by 1 / 32768, anything else as float32."""
     if isinstance(a, Pcm16):
         return a.f32()
+    if isinstance(a, DeviceAudio):
+        return a.numpy()
     return np.asarray(a, dtype=np.float32)
 
 
@@ -116,6 +136,87 @@ def _read_wav(path: Path, keep_pcm16: bool = False):
     else:
         raise ValueError(f"{path}: unsupported WAVE format tag {tag} with {bits}-bit samples")
     return x.reshape(-1, ch).mean(axis=1).astype(np.float32), sr
+
+
+def read_wav_channels(path) -> tuple[np.ndarray, int, str]:
+    """RIFF/WAVE -> (float32[channels, frames], rate, sample format) with the channels kept
+    (``_read_wav`` averages them): what the renderer and the peak check need (the reference
+    reads ``soundfile.read(always_2d=True)``, loudness.py:60).  Same formats and scaling as
+    ``_read_wav``; the format is "pcm8" / "pcm16" / "pcm24" / "pcm32" / "float32" / "float64"."""
+    data = Path(path).read_bytes()
+    if len(data) < 12 or data[:4] not in (b"RIFF", b"RF64") or data[8:12] != b"WAVE":
+        raise ValueError(f"{path}: not a RIFF/WAVE file")
+    fmt = raw = None
+    pos = 12
+    while pos + 8 <= len(data):
+        cid, size = data[pos:pos + 4], int.from_bytes(data[pos + 4:pos + 8], "little")
+        if cid == b"fmt ":
+            fmt = data[pos + 8:pos + 8 + size]
+        elif cid == b"data":
+            raw = data[pos + 8:pos + 8 + size]
+        pos += 8 + size + (size & 1)
+    if fmt is None or raw is None or len(fmt) < 16:
+        raise ValueError(f"{path}: WAVE file without fmt/data chunks")
+    tag, ch = int.from_bytes(fmt[0:2], "little"), int.from_bytes(fmt[2:4], "little")
+    sr, block_align = int.from_bytes(fmt[4:8], "little"), int.from_bytes(fmt[12:14], "little")
+    if tag == _WAVE_EXTENSIBLE and len(fmt) >= 26:
+        tag = int.from_bytes(fmt[24:26], "little")
+    if ch <= 0 or block_align <= 0 or block_align % ch:
+        raise ValueError(f"{path}: invalid WAVE header (channels={ch}, block_align={block_align})")
+    width = block_align // ch
+    raw = raw[:len(raw) // block_align * block_align]
+    if tag == _WAVE_FLOAT and width in (4, 8):
+        x, name = np.frombuffer(raw, "<f4" if width == 4 else "<f8").astype(np.float32), f"float{8 * width}"
+    elif tag == _WAVE_PCM and width == 1:
+        x, name = (np.frombuffer(raw, np.uint8).astype(np.float32) - 128.0) / 128.0, "pcm8"
+    elif tag == _WAVE_PCM and width == 2:
+        x, name = np.frombuffer(raw, "<i2").astype(np.float32) / 32768.0, "pcm16"
+    elif tag == _WAVE_PCM and width == 3:
+        b = np.frombuffer(raw, np.uint8).reshape(-1, 3).astype(np.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        x, name = np.where(v >= 1 << 23, v - (1 << 24), v).astype(np.float32) / float(1 << 23), "pcm24"
+    elif tag == _WAVE_PCM and width == 4:
+        x, name = (np.frombuffer(raw, "<i4").astype(np.float64) / 2147483648.0).astype(np.float32), "pcm32"
+    else:
+        raise ValueError(f"{path}: unsupported WAVE format tag {tag} with {8 * width}-bit samples")
+    return np.ascontiguousarray(x.reshape(-1, ch).T, dtype=np.float32), sr, name
+
+
+def quantize_pcm16(x: np.ndarray) -> tuple[np.ndarray, int]:
+    """(int16 clamp(rint(x 32768), -32768, 32767), samples clamped): the host statement of
+    ``nc_f32_to_pcm16`` (round half to even; x 32768 is exact in float32)."""
+    v = np.rint(np.asarray(x, np.float32) * np.float32(32768.0))
+    clipped = int(np.count_nonzero((v > 32767.0) | (v < -32768.0)))
+    return np.clip(v, -32768.0, 32767.0).astype(np.int16), clipped
+
+
+def write_wav(path, data, sr: int, sample_format: str = "float32") -> None:
+    """Write ``data`` ([channels, frames] or [frames]) as a RIFF/WAVE file of 16-bit PCM
+    ("pcm16") or IEEE float32 ("float32").  int16 data is written as stored (the renderer
+    quantises on the device, ``nc_f32_to_pcm16``); float data going to "pcm16" is quantised
+    here by the same rule (``quantize_pcm16``).  File encode, like decode, stays on the CPU."""
+    a = np.asarray(data)
+    if a.ndim == 1:
+        a = a[None, :]
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[0] > 65535:
+        raise ValueError("write_wav: data must be [frames] or [channels, frames]")
+    if sample_format == "pcm16":
+        q = a if a.dtype == np.int16 else quantize_pcm16(a)[0]
+        body, tag, width = np.ascontiguousarray(q.T).astype("<i2").tobytes(), _WAVE_PCM, 2
+    elif sample_format == "float32":
+        if a.dtype == np.int16:
+            raise ValueError("write_wav: int16 data is 16-bit PCM, not float32")
+        body, tag, width = np.ascontiguousarray(a.T).astype("<f4").tobytes(), _WAVE_FLOAT, 4
+    else:
+        raise ValueError(f"write_wav: sample format {sample_format!r} is not supported (pcm16, float32)")
+    ch = a.shape[0]
+    if len(body) + 36 >= 1 << 32:
+        raise ValueError("write_wav: more than 4 GiB of samples does not fit a RIFF file")
+    fmt = (tag.to_bytes(2, "little") + ch.to_bytes(2, "little") + int(sr).to_bytes(4, "little")
+           + (int(sr) * ch * width).to_bytes(4, "little") + (ch * width).to_bytes(2, "little")
+           + (8 * width).to_bytes(2, "little"))
+    head = b"RIFF" + (36 + len(body)).to_bytes(4, "little") + b"WAVE" + b"fmt " + (16).to_bytes(4, "little") + fmt
+    Path(path).write_bytes(head + b"data" + len(body).to_bytes(4, "little") + body)
 
 
 def load_audio(path: str, sr: Optional[int] = SAMPLE_RATE, *, keep_pcm16: bool = False) -> tuple[np.ndarray, int]:

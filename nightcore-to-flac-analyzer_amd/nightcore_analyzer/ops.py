@@ -264,3 +264,89 @@ def resample_poly(eng: Engine, arrays: Sequence[np.ndarray], up: int, down: int)
              len(h), up, down, pre, eng.stream())
     hy = y.cpu().numpy()
     return [hy[o:o + n].copy() for o, n in zip(o_off, n_out)]
+
+
+# ------------------------------------------------------------------ speed render (speed.hip)
+from .engine import _ALIGN  # noqa: E402  (upload_signals' 64-sample file alignment)
+
+
+def speed_plan(factor: float, lengths: Sequence[int]) -> Tuple[int, np.ndarray]:
+    """(P, n_out[file]) of a speed render: P = round(factor 1e6), n_out = ceil(n 1e6 / P), from
+    the library's own ``nc_speed_out_len`` (the formula the kernel uses).  Needs no device."""
+    import ctypes as C
+    from . import _native
+    lib = _native.load()
+    n_in = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+    n_out = np.zeros(len(n_in), np.int64)
+    p = C.c_int64(0)
+    _native.check(lib.nc_speed_out_len(float(factor), n_in.ctypes.data, len(n_in), C.byref(p), n_out.ctypes.data),
+                  "nc_speed_out_len")
+    return int(p.value), n_out
+
+
+def speed_render_device(eng: Engine, src, factor: float):
+    """Every file of ``src`` (arrays, or ``DeviceSignals`` already in HBM) played ``factor`` times
+    faster (the renderer's definition: DESIGN.md, include/ncgpu.h R2), one launch, the result
+    left in HBM: (DeviceSignals of the renders, device float32 peak[file] = max |y|, P).  No
+    host synchronisation."""
+    from .engine import DeviceSignals
+    sig = src if isinstance(src, DeviceSignals) else eng.upload_signals(list(src))
+    n = sig.n_files
+    P, n_out = speed_plan(factor, sig.length)
+    pad = (n_out + _ALIGN - 1) // _ALIGN * _ALIGN
+    o_off = np.zeros(n, np.int64)
+    o_off[1:] = np.cumsum(pad)[:-1]
+    up = _Upload()
+    up.add("in_off", sig.off, np.int64)
+    up.add("in_len", sig.length, np.int64)
+    up.add("out_off", o_off, np.int64)
+    d = up.commit(eng.dev)
+    y = torch.zeros(max(_ALIGN, int(pad.sum())), dtype=torch.float32, device=eng.dev)
+    peak = torch.empty(max(1, n), dtype=torch.float32, device=eng.dev)
+    if n:
+        eng.call("nc_speed_render", sig.buf.data_ptr(), d["in_off"].data_ptr(), d["in_len"].data_ptr(), n, P,
+                 y.data_ptr(), d["out_off"].data_ptr(), int(n_out.max()), peak.data_ptr(), eng.stream())
+    return DeviceSignals(y, o_off, n_out), peak[:n], P
+
+
+def speed_render(eng: Engine, arrays: Sequence[np.ndarray], factor: float) -> Tuple[List[np.ndarray], np.ndarray]:
+    """(renders, peaks): each array played ``factor`` times faster, and max |y| of each."""
+    out, peak, _ = speed_render_device(eng, [np.asarray(a, np.float32) for a in arrays], factor)
+    hy = out.buf.cpu().numpy()
+    return [hy[o:o + n].copy() for o, n in zip(out.off, out.length)], peak.cpu().numpy()
+
+
+def f32_to_pcm16_device(eng: Engine, sig, interleave: bool = False):
+    """16-bit PCM of the files of ``sig`` (DeviceSignals) by ``nc_f32_to_pcm16``: (device int16
+    buffer, offsets, device int32 clamped-sample counts).  ``interleave``: the files are the
+    equally long channels of one WAV file and come out frame-interleaved."""
+    n = sig.n_files
+    lens = np.asarray(sig.length, np.int64)
+    if interleave:
+        if n and not np.all(lens == lens[0]):
+            raise ValueError("interleaved channels must be equally long")
+        o_off, stride, total = np.arange(n, dtype=np.int64), max(1, n), int(lens.sum())
+    else:
+        pad = (lens + _ALIGN - 1) // _ALIGN * _ALIGN
+        o_off = np.zeros(n, np.int64)
+        o_off[1:] = np.cumsum(pad)[:-1]
+        stride, total = 1, int(pad.sum())
+    up = _Upload()
+    up.add("in_off", sig.off, np.int64)
+    up.add("in_len", lens, np.int64)
+    up.add("out_off", o_off, np.int64)
+    d = up.commit(eng.dev)
+    q = torch.zeros(max(_ALIGN, total), dtype=torch.int16, device=eng.dev)
+    clipped = torch.empty(max(1, n), dtype=torch.int32, device=eng.dev)
+    if n:
+        eng.call("nc_f32_to_pcm16", sig.buf.data_ptr(), d["in_off"].data_ptr(), d["in_len"].data_ptr(), n,
+                 int(lens.max()), q.data_ptr(), d["out_off"].data_ptr(), stride, clipped.data_ptr(), eng.stream())
+    return q, o_off, clipped[:n]
+
+
+def f32_to_pcm16(eng: Engine, arrays: Sequence[np.ndarray]) -> Tuple[List[np.ndarray], np.ndarray]:
+    """(int16 arrays, clamped-sample counts) of float32 arrays (``nc_f32_to_pcm16``)."""
+    sig = eng.upload_signals([np.asarray(a, np.float32) for a in arrays])
+    q, off, clipped = f32_to_pcm16_device(eng, sig)
+    hq = q.cpu().numpy()
+    return [hq[o:o + n].copy() for o, n in zip(off, sig.length)], clipped.cpu().numpy()

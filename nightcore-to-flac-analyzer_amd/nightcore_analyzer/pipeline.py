@@ -17,9 +17,9 @@ from typing import Callable, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from .consensus import AnalysisResult
-from .io import ENERGY_GATE_DB, HOP_SEC, SILENCE_STRIP_DB, WINDOW_SEC, load_audio
+from .io import ENERGY_GATE_DB, HOP_SEC, SILENCE_STRIP_DB, WINDOW_SEC, DeviceAudio, load_audio
 
-PathOrArray = Union[str, np.ndarray]
+PathOrArray = Union[str, np.ndarray, DeviceAudio]
 
 
 def _params(window_sec, hop_sec, energy_gate_db, silence_strip_db, src_trim_sec, auto_align, compute_pitch,
@@ -34,7 +34,9 @@ def _load(x: PathOrArray, log, what: str, sr: int = 22050):
     """A file decoded as load_audio does (a mono 16-bit WAV kept as its stored samples,
     io.Pcm16, and widened on the device at upload: half the PCIe bytes), or an array."""
     log(f"Loading {what} audio…")
-    if isinstance(x, np.ndarray):
+    if isinstance(x, DeviceAudio):          # a render already in HBM (render.refine_speed)
+        y = x
+    elif isinstance(x, np.ndarray):
         y = np.ascontiguousarray(x, dtype=np.float32)
     else:
         y, sr = load_audio(x, sr=sr, keep_pcm16=True)

@@ -1,0 +1,172 @@
+"""Render the sped-up source on the device and verify it in place: the part of the
+reference's workflow that shells out to ``sox SRC DST speed F`` (workflow.py:108-118),
+re-analyses the result against the nightcore and corrects the factor until the residual is
+inside tolerance (workflow.py:766-833), without its prompts and without a file round trip.
+
+PARITY UNPINNED: sox is not installed and the reference holds no resampler, so the
+renderer's definition is this project's own (``nc_speed_render`` in
+include/ncgpu.h): a Kaiser-windowed sinc (beta 10.06, 32 zero crossings a side, cut-off at
+0.9 of the lower Nyquist) evaluated at the exact rational position m P / 10^6 of every output.
+
+* ``speed`` / ``speed_file`` — the render of an array / of every channel of a WAV file.
+* ``refine_speed`` — render, re-analyse, correct; the render stays in HBM between the two.
+* ``quantize_factor`` / ``hqnc_path`` — the six-decimal factor and the output naming rule.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass, field
+from pathlib import Path
+from typing import Callable, List, Optional
+
+import numpy as np
+
+from .consensus import AnalysisResult
+from .io import DeviceAudio, as_f32, read_wav_channels, write_wav
+
+Q = 1_000_000            # the six decimals of `sox … speed {F:.6f}` (workflow.py:116)
+MIN_FACTOR, MAX_FACTOR = 0.25, 4.0
+IBI_TOLERANCE = 0.005    # |residual - 1| accepted when the IBI ratio is available (workflow.py:160)
+BPM_TOLERANCE = 0.02     # … when only the windowed tempo ratio is (workflow.py:381)
+
+
+def quantize_factor(factor: float) -> float:
+    """The factor the renderer really applies: round(F 10^6) / 10^6."""
+    f = float(factor)
+    if not math.isfinite(f) or not MIN_FACTOR <= f <= MAX_FACTOR:
+        raise ValueError(f"speed factor {factor!r} outside [{MIN_FACTOR}, {MAX_FACTOR}]")
+    return int(round(f * Q)) / Q
+
+
+def hqnc_path(hq, version: int = 0) -> Path:
+    """``Song [Nightcore].wav`` (version 0) or ``Song [Nightcore] UPD<version>.wav`` beside
+    ``hq`` (the reference's naming of the sped-up file and of its corrected re-renders)."""
+    hq = Path(hq)
+    tail = "" if int(version) == 0 else f" UPD{int(version)}"
+    return hq.with_name(f"{hq.stem} [Nightcore]{tail}{hq.suffix}")
+
+
+def _dbfs(peak: float) -> float:
+    return -math.inf if peak <= 0.0 else 20.0 * math.log10(peak)
+
+
+@dataclass
+class RenderInfo:
+    """What ``speed_file`` wrote."""
+    path: Path
+    factor: float              # the effective factor P / 10^6
+    n_out: int                 # frames written
+    channels: int
+    sample_rate: int
+    sample_format: str         # of the written file
+    peak: float                # max |sample| over all channels, before any 16-bit clamp
+    peak_dbfs: float
+    clipped_samples: int       # samples at or beyond full scale (clamped, in a 16-bit file)
+
+    @property
+    def is_clipping(self) -> bool:
+        return self.peak_dbfs >= 0.0
+
+
+def speed(y: np.ndarray, factor: float, sr: Optional[int] = None) -> np.ndarray:
+    """The mono signal ``y`` played ``factor`` times faster (float32, ceil(len / factor')
+    samples at the same rate, factor' = ``quantize_factor(factor)``).  ``sr`` is accepted for
+    symmetry with the other seams; the render does not depend on it."""
+    from .engine import get_engine
+    from .ops import speed_render
+    quantize_factor(factor)
+    (out,), _ = speed_render(get_engine(), [np.asarray(y, np.float32).reshape(-1)], factor)
+    return out
+
+
+def speed_file(src_path, dst_path, factor: float) -> RenderInfo:
+    """Render every channel of the WAV file ``src_path`` at its own rate and write
+    ``dst_path``: a 16-bit PCM source gives a 16-bit PCM file (quantised on the device,
+    ``nc_f32_to_pcm16``), anything else a float32 file."""
+    from .engine import get_engine
+    from .ops import f32_to_pcm16_device, speed_render_device
+    f = quantize_factor(factor)
+    data, sr, fmt = read_wav_channels(src_path)
+    eng = get_engine()
+    out, peak_d, P = speed_render_device(eng, list(data), f)
+    ch, n_out = data.shape[0], int(out.length[0])
+    if fmt == "pcm16":
+        q, _, clipped_d = f32_to_pcm16_device(eng, out, interleave=True)
+        frames = q[:ch * n_out].cpu().numpy().reshape(n_out, ch).T
+        clipped = int(clipped_d.sum().item())
+        out_fmt = "pcm16"
+    else:
+        hy = out.buf.cpu().numpy()
+        frames = np.stack([hy[o:o + n_out] for o in out.off])
+        clipped = int(np.count_nonzero(np.abs(frames) >= 1.0))
+        out_fmt = "float32"
+    write_wav(dst_path, frames, sr, out_fmt)
+    peak = float(peak_d.max().item()) if ch else 0.0
+    return RenderInfo(Path(dst_path), P / Q, n_out, ch, sr, out_fmt, peak, _dbfs(peak), clipped)
+
+
+@dataclass
+class Refinement:
+    """The verify-and-correct loop's record."""
+    factors: List[float] = field(default_factory=list)       # every factor rendered, in order
+    results: List[AnalysisResult] = field(default_factory=list)   # nightcore against each render
+    residuals: List[float] = field(default_factory=list)
+    converged: bool = False
+    estimator: str = "IBI"                                    # of the last residual: "IBI" or "BPM"
+    initial: Optional[AnalysisResult] = None                  # nightcore against the source (no ``start``)
+    render: Optional[DeviceAudio] = None                      # the last render, resident in HBM
+
+    @property
+    def factor(self) -> float:
+        return self.factors[-1]
+
+    @property
+    def corrections(self) -> int:
+        return max(0, len(self.factors) - 1)
+
+
+def refine_speed(nightcore, source, *, start: Optional[float] = None, max_renders: int = 4,
+                 log: Optional[Callable[[str], None]] = None) -> Refinement:
+    """The workflow's create-verify-correct loop (workflow.py:766-833) on the 22 050 Hz mono
+    analysis copies.  First factor: ``start``, else the IBI ratio of nightcore against source,
+    else their tempo ratio.  Each pass renders the source at the factor on the device,
+    analyses the nightcore against the render (``pipeline.run(compute_pitch=False)``; the
+    render never leaves HBM) and takes the residual (IBI ratio, else tempo ratio); inside
+    tolerance (0.5 % IBI, 2 % BPM) it stops, otherwise factor <- quantize(factor residual)."""
+    from . import pipeline
+    from .engine import get_engine
+    from .ops import speed_render_device
+
+    def _log(msg: str) -> None:
+        if log is not None:
+            log(msg)
+
+    if max_renders < 1:
+        raise ValueError("refine_speed: max_renders must be at least 1")
+    nc = as_f32(pipeline._load(nightcore, _log, "nightcore"))
+    src = as_f32(pipeline._load(source, _log, "source"))
+    out = Refinement()
+    if start is None:
+        out.initial = pipeline.run(nc, src, compute_pitch=False, log=log)
+        start = out.initial.ibi_ratio if out.initial.ibi_ratio is not None else out.initial.tempo_ratio
+    factor = quantize_factor(start)
+    eng = get_engine()
+    resident = eng.upload_signals([src])
+    for k in range(max_renders):
+        _log(f"Render {k + 1}: speed {factor:.6f}×")
+        rendered, _, _ = speed_render_device(eng, resident, factor)
+        out.render = DeviceAudio(rendered.buf[:int(rendered.length[0])])
+        out.factors.append(factor)
+        res = pipeline.run(nc, out.render, compute_pitch=False, log=log)
+        out.results.append(res)
+        ibi = res.ibi_ratio is not None
+        residual = float(res.ibi_ratio if ibi else res.tempo_ratio)
+        out.residuals.append(residual)
+        out.estimator = "IBI" if ibi else "BPM"
+        _log(f"  residual ({out.estimator}): {residual:.6f}  ({(residual - 1.0) * 100:+.2f} %)")
+        if abs(residual - 1.0) < (IBI_TOLERANCE if ibi else BPM_TOLERANCE):
+            out.converged = True
+            break
+        if k + 1 < max_renders:
+            factor = quantize_factor(factor * residual)
+    return out
