@@ -667,8 +667,11 @@ int launch_tempo_beats(Context& ctx, BeatArgs a, int n_seq, int max_len, hipStre
       set_error("tempo_beats: long sequences need the global workspace");
       return -3;
     }
-    // LDS ring of cumulative scores: >= dmax + B = 2P + round(P/2) frames, P <= acw - 1
-    int ring = 1;
+    // LDS ring of cumulative scores: >= dmax + B = 2P + round(P/2) frames, P <= acw - 1, and
+    // never shorter than one DP window (the kernel copies a finished window out of the ring;
+    // a short tempogram window, acw <= 204, would otherwise end in the capacity error)
+    static_assert((kBeatWin & (kBeatWin - 1)) == 0, "the ring is indexed with a mask");
+    int ring = kBeatWin;
     while (ring < (a.tab_cap / 2) * 5 / 2 + 2) ring <<= 1;
     a.ring_cap = ring;
     const size_t lds = tab + (size_t)ring * sizeof(double) + (size_t)kBeatWin * (sizeof(double) + sizeof(int));

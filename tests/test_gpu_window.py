@@ -6,6 +6,7 @@ import torch
 
 from oracle import ncref, refglue
 from nightcore_analyzer import _dev, synth
+from beat_launch import run_beats
 
 pytestmark = pytest.mark.gpu
 
@@ -51,29 +52,8 @@ def test_window_stage_matches_oracle(gpu_ctx):
 
 
 def _run_beats(ctx, onset, tg, start_bpm, hop=512):
-    dev = _dev.device(0)
-    n, T = onset.shape
-    acw = tg.shape[1]
-    d_on = _dev.to_dev(onset.reshape(-1), dev, np.float32)
-    d_tg = _dev.to_dev(tg.reshape(-1), dev, np.float64)
-    off = _dev.to_dev(np.arange(n, dtype=np.int64) * T, dev)
-    ln = _dev.to_dev(np.full(n, T, np.int32), dev)
-    sb = _dev.to_dev(np.asarray(start_bpm, np.float64), dev)
-    bpm = _dev.empty(n, torch.float64, dev)
-    lag = _dev.empty(n, torch.int32, dev)
-    nb = _dev.empty(n, torch.int32, dev)
-    mg = _dev.empty(n, torch.float64, dev)
-    beats = _dev.empty(n * T, torch.int32, dev)
-    total = n * T
-    wsb = ctx.lib.nc_tempo_beats_workspace_bytes(total)
-    ws = _dev.workspace(wsb, dev)
-    ctx.call("nc_tempo_beats", d_on.data_ptr(), off.data_ptr(), ln.data_ptr(), n, T, d_tg.data_ptr(),
-             acw, sb.data_ptr(), None, None, hop, 1, bpm.data_ptr(), lag.data_ptr(), nb.data_ptr(),
-             mg.data_ptr(), beats.data_ptr(), total, ws.data_ptr(), wsb, _dev.stream_handle())
-    torch.cuda.synchronize()
-    b = beats.cpu().numpy().reshape(n, T)
-    nbv = nb.cpu().numpy()
-    return bpm.cpu().numpy(), lag.cpu().numpy(), nbv, [b[i, :max(0, nbv[i])] for i in range(n)]
+    out = run_beats(ctx, [np.asarray(o, np.float32) for o in onset], tg, start_bpm, hop=hop)
+    return out.bpm, out.lag, out.nbeats, out.beats
 
 
 @pytest.mark.parametrize("prior", [120.0, 153.80859375])
