@@ -14,73 +14,26 @@
 // and every sum slides one frame in O(1):
 //   Zm(t+1) = e^{-i m theta} (Zm(t) - p_k[t] + e^{i m theta L} p_k[t+L]),  e^{i m theta L} = e^{-i m theta k}.
 // All arithmetic is f64: about 28 flops per (lag, frame), against two 2N-point
-// FFTs per frame, and agreement with librosa's f64 FFT autocorrelation at the
-// 1e-15 level (tests/test_oracle_known_answers.py checks the identity).
+// FFTs per frame.  Agreement with librosa's f64 FFT autocorrelation is at the 1e-15
+// level while the envelope keeps a bounded dynamic range between two seeds
+// (tests/test_oracle_known_answers.py checks the identity) -- and only then.  The sums
+// are slid by subtraction, so their rounding residue is proportional to the loudest
+// passage they have held, while the normaliser 1 / ac_t[0] follows the current frame:
+// once the envelope falls to exact zero (every mel band under the top_db clamp: a gap, a
+// fade to digital silence), the frames that still see the last samples under the far tail
+// of the Hann window (weight ~ (pi j / N)^4) divide that residue by an ac_t[0] twelve or
+// more decades smaller, and the mean is off by 1e-3 and more.  Remedy (slide_lag_sum[2]): the
+// five sums are recomputed directly (slide_seed) at every frame whose ac_t[0] has fallen
+// below SLIDE_RESEED = 2^-20 of the largest one since the last seed -- two or three extra
+// seeds per fall, an error near 1e-7 at the worst instead (tests/tempo_feature_cases.py
+// restates the rule, tests/test_gpu_tempo_features.py holds the kernels to it).  ac_t[0] is
+// the same for every lag, so all threads of a block re-seed at the same frames, and the
+// decision uses frames of the current [t0, t1) only: a tile's row does not depend on which
+// launch computes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace nc {
-
-// sum_{t0 <= t < t1} ac_t[k] * rinv(t); x(i) returns the padded envelope (float),
-// valid for t0 <= i < t1 - 1 + N + 1.
-template <class XF, class RF>
-__device__ __forceinline__ double slide_lag_sum(const XF& x, const RF& rinv, int N, int k, int t0, int t1) {
-  const double inv_half = 2.0 / (double)N;  // theta / pi
-  double s1, c1, sk, ck;
-  sincospi(inv_half, &s1, &c1);
-  sincospi((double)k * inv_half, &sk, &ck);
-  const double c2 = fma(c1, c1, -s1 * s1), s2 = 2.0 * c1 * s1;
-  const double ck2 = fma(ck, ck, -sk * sk), sk2 = 2.0 * ck * sk;
-  const double A = 0.25 + 0.125 * ck, B = -0.25 - 0.25 * ck, C = 0.25 * sk, D = 0.125 * ck, E = -0.125 * sk;
-  const int L = N - k;
-
-  double S0 = 0.0, z1r = 0.0, z1i = 0.0, z2r = 0.0, z2i = 0.0;
-  for (int j0 = 0; j0 < L; j0 += 64) {
-    double es, ec;  // e^{i theta j}, re-seeded every 64 terms
-    sincospi((double)j0 * inv_half, &es, &ec);
-    const int je = min(L, j0 + 64);
-    for (int j = j0; j < je; ++j) {
-      const double p = (double)x(t0 + j) * (double)x(t0 + j + k);
-      const double e2c = fma(ec, ec, -es * es), e2s = 2.0 * ec * es;
-      S0 += p;
-      z1r = fma(ec, p, z1r);
-      z1i = fma(es, p, z1i);
-      z2r = fma(e2c, p, z2r);
-      z2i = fma(e2s, p, z2i);
-      const double nc = fma(ec, c1, -es * s1), ns = fma(es, c1, ec * s1);
-      ec = nc;
-      es = ns;
-    }
-  }
-  double acc = 0.0;
-  // operands of frame t are loaded one frame ahead (software pipelining: the LDS latency
-  // overlaps the previous frame's arithmetic); x must be readable up to t1 + N
-  double xt = (double)x(t0), xk = (double)x(t0 + k), xl = (double)x(t0 + L), xn = (double)x(t0 + N);
-  double r = rinv(t0);
-  for (int t = t0; t < t1; ++t) {
-    const int tn = t + 1 < t1 ? t + 1 : t;
-    const double xt1 = (double)x(tn), xk1 = (double)x(tn + k), xl1 = (double)x(tn + L), xn1 = (double)x(tn + N);
-    const double r1 = rinv(tn);
-    const double ac = fma(E, z2i, fma(D, z2r, fma(C, z1i, fma(B, z1r, A * S0))));
-    acc = fma(ac, r, acc);
-    const double pt = xt * xk;
-    const double pl = xl * xn;
-    xt = xt1;
-    xk = xk1;
-    xl = xl1;
-    xn = xn1;
-    r = r1;
-    S0 = (S0 - pt) + pl;
-    // (u) * e^{-i m theta}:  (a + ib)(c - is) = (ac + bs) + i(bc - as)
-    const double u1r = fma(ck, pl, z1r - pt), u1i = fma(-sk, pl, z1i);
-    z1r = fma(u1r, c1, u1i * s1);
-    z1i = fma(u1i, c1, -u1r * s1);
-    const double u2r = fma(ck2, pl, z2r - pt), u2i = fma(-sk2, pl, z2i);
-    z2r = fma(u2r, c2, u2i * s2);
-    z2i = fma(u2i, c2, -u2r * s2);
-  }
-  return acc;
-}
 
 // Per-lag state of the sliding sums (see the header comment).
 struct SlideLag {
@@ -90,29 +43,18 @@ struct SlideLag {
   int k, L;
 };
 
+// the five sums of frame t, directly
 template <class XF>
-__device__ __forceinline__ void slide_init(SlideLag& s, const XF& x, int N, int k, int t0, double c1, double s1) {
+__device__ __forceinline__ void slide_seed(SlideLag& s, const XF& x, int N, int t, double c1, double s1) {
   const double inv_half = 2.0 / (double)N;
-  double sk, ck;
-  sincospi((double)k * inv_half, &sk, &ck);
-  s.k = k;
-  s.L = N - k;
-  s.ck = ck;
-  s.sk = sk;
-  s.ck2 = fma(ck, ck, -sk * sk);
-  s.sk2 = 2.0 * ck * sk;
-  s.A = 0.25 + 0.125 * ck;
-  s.B = -0.25 - 0.25 * ck;
-  s.C = 0.25 * sk;
-  s.D = 0.125 * ck;
-  s.E = -0.125 * sk;
+  const int k = s.k;
   double S0 = 0.0, z1r = 0.0, z1i = 0.0, z2r = 0.0, z2i = 0.0;
   for (int j0 = 0; j0 < s.L; j0 += 64) {
     double es, ec;  // e^{i theta j}, re-seeded every 64 terms
     sincospi((double)j0 * inv_half, &es, &ec);
     const int je = min(s.L, j0 + 64);
     for (int j = j0; j < je; ++j) {
-      const double p = (double)x(t0 + j) * (double)x(t0 + j + k);
+      const double p = (double)x(t + j) * (double)x(t + j + k);
       const double e2c = fma(ec, ec, -es * es), e2s = 2.0 * ec * es;
       S0 += p;
       z1r = fma(ec, p, z1r);
@@ -131,6 +73,23 @@ __device__ __forceinline__ void slide_init(SlideLag& s, const XF& x, int N, int 
   s.z2i = z2i;
 }
 
+__device__ __forceinline__ void slide_coeffs(SlideLag& s, int N, int k) {
+  const double inv_half = 2.0 / (double)N;
+  double sk, ck;
+  sincospi((double)k * inv_half, &sk, &ck);
+  s.k = k;
+  s.L = N - k;
+  s.ck = ck;
+  s.sk = sk;
+  s.ck2 = fma(ck, ck, -sk * sk);
+  s.sk2 = 2.0 * ck * sk;
+  s.A = 0.25 + 0.125 * ck;
+  s.B = -0.25 - 0.25 * ck;
+  s.C = 0.25 * sk;
+  s.D = 0.125 * ck;
+  s.E = -0.125 * sk;
+}
+
 __device__ __forceinline__ double slide_ac(const SlideLag& s) {
   return fma(s.E, s.z2i, fma(s.D, s.z2r, fma(s.C, s.z1i, fma(s.B, s.z1r, s.A * s.S0))));
 }
@@ -147,8 +106,52 @@ __device__ __forceinline__ void slide_step(SlideLag& s, double pt, double pl, do
   s.z2i = fma(u2i, c2, -u2r * s2);
 }
 
+// ac_t[0] below this fraction of the largest one since the last seed: seed again
+constexpr double SLIDE_RESEED = 1.0 / 1048576.0;  // 2^-20
+
+// sum_{t0 <= t < t1} ac_t[k] * rinv(t); x(i) returns the padded envelope (float), valid for
+// t0 <= i <= t1 - 1 + N.  The frames are walked in runs: each run starts from directly
+// computed sums (slide_seed) and slides until the re-seeding rule of the header comment ends
+// it.  rmin is the smallest rinv (largest ac_t[0]) of the run; frames whose ac_t[0] is below
+// tiny (rinv = 1, tg_rinv) neither end a run nor count.
+template <class XF, class RF>
+__device__ __forceinline__ double slide_lag_sum(const XF& x, const RF& rinv, int N, int k, int t0, int t1) {
+  double s1, c1;
+  sincospi(2.0 / (double)N, &s1, &c1);
+  const double c2 = fma(c1, c1, -s1 * s1), s2 = 2.0 * c1 * s1;
+  SlideLag a;
+  slide_coeffs(a, N, k);
+  double acc = 0.0;
+  int t = t0;
+  while (t < t1) {
+    slide_seed(a, x, N, t, c1, s1);
+    // operands of frame t are loaded one frame ahead (software pipelining: the LDS latency
+    // overlaps the previous frame's arithmetic); x must be readable up to t1 - 1 + N
+    double xt = (double)x(t), xk = (double)x(t + k), xl = (double)x(t + a.L), xn = (double)x(t + N);
+    double r = rinv(t), rmin = r != 1.0 ? r : INFINITY;
+    for (;;) {
+      const int tn = t + 1 < t1 ? t + 1 : t;
+      const double xt1 = (double)x(tn), xk1 = (double)x(tn + k), xl1 = (double)x(tn + a.L), xn1 = (double)x(tn + N);
+      const double r1 = rinv(tn);
+      acc = fma(slide_ac(a), r, acc);
+      slide_step(a, xt * xk, xl * xn, c1, s1, c2, s2);
+      xt = xt1;
+      xk = xk1;
+      xl = xl1;
+      xn = xn1;
+      r = r1;
+      if (++t >= t1) break;
+      if (r != 1.0) {
+        if (r * SLIDE_RESEED > rmin) break;
+        rmin = fmin(rmin, r);
+      }
+    }
+  }
+  return acc;
+}
+
 // Two lags at once (independent dependency chains interleaved; the x(t) and rinv(t)
-// reads are shared).  Same arithmetic per lag as slide_lag_sum.
+// reads are shared).  Same arithmetic per lag, same runs as slide_lag_sum.
 template <class XF, class RF>
 __device__ __forceinline__ void slide_lag_sum2(const XF& x, const RF& rinv, int N, int ka, int kb, int t0, int t1,
                                                double& acc_a, double& acc_b) {
@@ -156,27 +159,37 @@ __device__ __forceinline__ void slide_lag_sum2(const XF& x, const RF& rinv, int 
   sincospi(2.0 / (double)N, &s1, &c1);
   const double c2 = fma(c1, c1, -s1 * s1), s2 = 2.0 * c1 * s1;
   SlideLag a, b;
-  slide_init(a, x, N, ka, t0, c1, s1);
-  slide_init(b, x, N, kb, t0, c1, s1);
+  slide_coeffs(a, N, ka);
+  slide_coeffs(b, N, kb);
   double ra = 0.0, rb = 0.0;
-  // operands loaded one frame ahead (see slide_lag_sum)
-  double xt = (double)x(t0), xn = (double)x(t0 + N), xka = (double)x(t0 + ka), xkb = (double)x(t0 + kb);
-  double xla = (double)x(t0 + a.L), xlb = (double)x(t0 + b.L), r = rinv(t0);
-  for (int t = t0; t < t1; ++t) {
-    const int tn = t + 1 < t1 ? t + 1 : t;
-    const double xt1 = (double)x(tn), xn1 = (double)x(tn + N), xka1 = (double)x(tn + ka), xkb1 = (double)x(tn + kb);
-    const double xla1 = (double)x(tn + a.L), xlb1 = (double)x(tn + b.L), r1 = rinv(tn);
-    ra = fma(slide_ac(a), r, ra);
-    rb = fma(slide_ac(b), r, rb);
-    slide_step(a, xt * xka, xla * xn, c1, s1, c2, s2);
-    slide_step(b, xt * xkb, xlb * xn, c1, s1, c2, s2);
-    xt = xt1;
-    xn = xn1;
-    xka = xka1;
-    xkb = xkb1;
-    xla = xla1;
-    xlb = xlb1;
-    r = r1;
+  int t = t0;
+  while (t < t1) {
+    slide_seed(a, x, N, t, c1, s1);
+    slide_seed(b, x, N, t, c1, s1);
+    // operands loaded one frame ahead (see slide_lag_sum)
+    double xt = (double)x(t), xn = (double)x(t + N), xka = (double)x(t + ka), xkb = (double)x(t + kb);
+    double xla = (double)x(t + a.L), xlb = (double)x(t + b.L), r = rinv(t), rmin = r != 1.0 ? r : INFINITY;
+    for (;;) {
+      const int tn = t + 1 < t1 ? t + 1 : t;
+      const double xt1 = (double)x(tn), xn1 = (double)x(tn + N), xka1 = (double)x(tn + ka), xkb1 = (double)x(tn + kb);
+      const double xla1 = (double)x(tn + a.L), xlb1 = (double)x(tn + b.L), r1 = rinv(tn);
+      ra = fma(slide_ac(a), r, ra);
+      rb = fma(slide_ac(b), r, rb);
+      slide_step(a, xt * xka, xla * xn, c1, s1, c2, s2);
+      slide_step(b, xt * xkb, xlb * xn, c1, s1, c2, s2);
+      xt = xt1;
+      xn = xn1;
+      xka = xka1;
+      xkb = xkb1;
+      xla = xla1;
+      xlb = xlb1;
+      r = r1;
+      if (++t >= t1) break;
+      if (r != 1.0) {
+        if (r * SLIDE_RESEED > rmin) break;
+        rmin = fmin(rmin, r);
+      }
+    }
   }
   acc_a = ra;
   acc_b = rb;

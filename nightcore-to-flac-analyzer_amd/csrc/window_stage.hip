@@ -218,6 +218,44 @@ __device__ __forceinline__ void wtg_rinv_blocked(const double* sh_x, const doubl
   }
 }
 
+// The six correlations difference prefix sums of the frame normalisers 1 / ac_t[0].  Where
+// those span too many decades (a window that falls to exact zero and comes back: the frames
+// that see only the last samples under the far tail of the Hann window have a normaliser up to
+// (N / pi)^4 times the others'), the sums lose the small terms: measured on the 24 s window of
+// tests/test_gpu_tempo_features.py with 12 s of digital silence, 1.6e-4 in the tempogram mean
+// at a spread of 7e14, growing in proportion to the spread (~1e-18 x spread in the numpy
+// restatement).  One check per workgroup: largest / smallest ac_t[0] at or above tiny beyond
+// WTG_SPREAD = 2^36 (error bound ~1e-7).  Music keeps the spread below 1e4.
+constexpr double WTG_SPREAD = 68719476736.0;  // 2^36
+
+// Called right after wtg_rinv_blocked: every thread looks at the normalisers it wrote itself,
+// and the one barrier in here is also the one that publishes sh_rinv to the workgroup.
+template <int NT>
+__device__ __forceinline__ bool wtg_ill_conditioned(const double* sh_rinv, int T, BlockScratch<NT>& red) {
+  double hi = 0.0, lo = INFINITY;  // of rinv; frames below tiny carry rinv = 1 (tg_rinv) and do not count
+  for (int t = threadIdx.x; t < T; t += NT) {
+    const double r = sh_rinv[t];
+    if (r != 1.0) {
+      hi = fmax(hi, r);
+      lo = fmin(lo, r);
+    }
+  }
+  hi = wave_max(hi);
+  lo = -wave_max(-lo);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    red.d[wave] = hi;
+    red.l[wave] = __double_as_longlong(lo);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < NT / 64; ++i) {
+    hi = fmax(hi, red.d[i]);
+    lo = fmin(lo, __longlong_as_double(red.l[i]));
+  }
+  return hi > lo * WTG_SPREAD;
+}
+
 __global__ __launch_bounds__(WT_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void window_tg_kernel(WinTgArgs a) {
   const Span span_(a.span);
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -245,7 +283,17 @@ __global__ __launch_bounds__(WT_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
   }
   wtg_onset<WT_THREADS>(a, w, sh_x, red);
   wtg_rinv_blocked<WT_THREADS>(sh_x, sh_wsq, T, acw, seq, sh_q, sh_rinv);
-  __syncthreads();
+  if (wtg_ill_conditioned<WT_THREADS>(sh_rinv, T, red)) {
+    // the prefix sums of the normalisers would be swamped by their largest terms: this window
+    // takes the re-seeding sliding sums (nc_slide.h), one lag per thread, x and rinv where
+    // they are (x is zero beyond its pad, slide_lag_sum reads x[T - 1 + acw]).  The branch is
+    // block-uniform.
+    auto xf = [&](int i) { return sh_x[i]; };
+    auto rf = [&](int t) { return sh_rinv[t]; };
+    for (int k = tid; k < acw; k += WT_THREADS)
+      a.tg_out[(size_t)w * acw + k] = slide_lag_sum(xf, rf, acw, k, 0, T) / (double)T;
+    return;
+  }
   tgc_prefix(sh_rinv, sh_cs, T, acw, sh_q, tid, WT_THREADS);
   __syncthreads();
   tgc_sequences(sh_x, sh_q, sh_cs, T, acw, L.U, seq, tid, WT_THREADS);
@@ -262,7 +310,7 @@ __global__ __launch_bounds__(WT_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
 }
 
 // Windows whose correlation sequences do not fit in LDS (window_sec above ~29 s): the
-// sliding sums of nc_slide.h, lags k and acw-1-k per thread (equal start-up work).
+// re-seeding sliding sums of nc_slide.h, lags k and acw-1-k per thread (equal start-up work).
 constexpr int WS_THREADS = 192;
 __host__ __device__ inline size_t wtg_slide_lds_doubles(int T, int acw) { return (size_t)T + (T + acw) + 2 * (size_t)acw; }
 

@@ -7,6 +7,8 @@ import scipy.signal
 
 from oracle import ncref, refglue
 from nightcore_analyzer import synth
+from tempo_feature_cases import (correlation_tempogram_mean as _correlation_tempogram_mean,
+                                 sliding_tempogram_mean as _sliding_tempogram_mean)
 
 SR = 22050
 
@@ -81,37 +83,6 @@ def test_mel_filterbank_slaney_properties():
     assert (np.count_nonzero(W, axis=0) <= 2).all() and (np.count_nonzero(W, axis=1) > 0).all()
 
 
-def _sliding_tempogram_mean(o, N):
-    """The engine's tempogram algorithm (csrc/nc_slide.h) in numpy: five sliding
-    f64 sums per lag instead of one FFT autocorrelation per frame."""
-    T, p = len(o), N // 2
-    x = np.pad(o, (p, p), mode="linear_ramp", end_values=(0, 0)).astype(np.float64)
-    w2 = ncref.hann(N).astype(np.float64) ** 2
-    ac0 = np.array([np.dot(w2, x[t:t + N] ** 2) for t in range(T)])
-    rinv = np.where(ac0 < np.finfo(np.float64).tiny, 1.0, 1.0 / np.where(ac0 == 0, 1, ac0))
-    th = 2 * np.pi / N
-    k = np.arange(N)
-    L = N - k
-    c, s = np.cos(th * k), np.sin(th * k)
-    A, B, C, D, E = 0.25 + 0.125 * c, -0.25 - 0.25 * c, 0.25 * s, 0.125 * c, -0.125 * s
-    j = np.arange(N)[:, None]
-    P = x[j] * x[np.minimum(j + k[None, :], len(x) - 1)] * (j < L[None, :])   # p_k[j], masked to j < L
-    S0 = P.sum(0)
-    Z1 = (np.exp(1j * th * j) * P).sum(0)
-    Z2 = (np.exp(2j * th * j) * P).sum(0)
-    e1L, e2L = np.exp(-1j * th * k), np.exp(-2j * th * k)
-    acc = np.zeros(N)
-    for t in range(T):
-        ac = A * S0 + B * Z1.real + C * Z1.imag + D * Z2.real + E * Z2.imag
-        acc += ac * rinv[t]
-        pt = x[t] * x[t + k]
-        pl = x[t + L] * x[t + N]
-        S0 = S0 - pt + pl
-        Z1 = np.exp(-1j * th) * (Z1 - pt + e1L * pl)
-        Z2 = np.exp(-2j * th) * (Z2 - pt + e2L * pl)
-    return acc / T
-
-
 @pytest.mark.parametrize("seed", [0, 1])
 def test_sliding_tempogram_identity_matches_fft_autocorrelation(seed):
     """w[j]w[j+k] is a degree-2 trigonometric polynomial in j, so the Hann-windowed
@@ -121,41 +92,6 @@ def test_sliding_tempogram_identity_matches_fft_autocorrelation(seed):
     ref = ncref.tempogram_mean(o, 344)
     got = _sliding_tempogram_mean(o, 344)
     assert np.max(np.abs(got - ref)) < 1e-12
-
-
-def _correlation_tempogram_mean(o, N):
-    """The engine's window tempogram (csrc/nc_tgcorr.h) in numpy: prefix sums of the frame
-    normalisers, six sequences, and per lag three Hankel minus three Toeplitz correlations
-    weighted by (1, cos theta k, sin theta k)."""
-    T, p = len(o), N // 2
-    x = np.pad(o, (p, p), mode="linear_ramp", end_values=(0, 0)).astype(np.float64)
-    U = T + N
-    x = np.concatenate([x, np.zeros(U - len(x))])
-    w2 = ncref.hann(N).astype(np.float64) ** 2
-    ac0 = np.array([np.dot(w2, x[t:t + N] ** 2) for t in range(T)])
-    r = np.where(ac0 < np.finfo(np.float64).tiny, 1.0, 1.0 / np.where(ac0 == 0, 1, ac0))
-    th = 2 * np.pi / N
-    t = np.arange(T)
-    Q = [np.concatenate([[0.0], np.cumsum(r * f)])
-         for f in (np.ones(T), np.cos(th * t), np.sin(th * t), np.cos(2 * th * t), np.sin(2 * th * t))]
-    u = np.arange(U)
-    cu, su, c2u, s2u = np.cos(th * u), np.sin(th * u), np.cos(2 * th * u), np.sin(2 * th * u)
-
-    def g(at):
-        P0, Qc1, Qs1, Qc2, Qs2 = (q[at] for q in Q)
-        P1, P2 = cu * Qc1 + su * Qs1, su * Qc1 - cu * Qs1
-        P3, P4 = c2u * Qc2 + s2u * Qs2, s2u * Qc2 - c2u * Qs2
-        return [(P0 - P1) / 4, P0 / 8 - P1 / 4 + P3 / 8, P2 / 4 - P4 / 8]
-
-    a = [x * v for v in g(np.minimum(T - 1, u) + 1)]
-    b = [x * v for v in g(np.maximum(0, u - N + 1))]
-    b[2] = -b[2]
-    out = np.zeros(N)
-    for k in range(N):
-        n = U - k
-        d = [np.dot(a[i][:n], x[k:]) - np.dot(b[i][k:], x[:n]) for i in range(3)]
-        out[k] = d[0] + np.cos(th * k) * d[1] + np.sin(th * k) * d[2]
-    return out / T
 
 
 @pytest.mark.parametrize("quiet", [None, 1e-3, 1e-6])
