@@ -23,13 +23,12 @@ from __future__ import annotations
 
 import gc
 import logging
-import math
 import os
 import threading
 import time
 import weakref
 from dataclasses import dataclass, field
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -77,7 +76,8 @@ def percentile_params(n_boot: int, ci: float) -> Tuple[float, float, float, floa
     return tuple(out)
 
 
-PEAK_SLOTS = 192   # piptrack peak slots per tuning frame (csrc/nc_piptrack.h kPeakSlots)
+_BOOT_PCT = percentile_params(C.N_BOOTSTRAP, C.CI_LEVEL)   # of the pipelined groups' bootstraps
+PEAK_SLOTS = 192  # piptrack peak slots per tuning frame (csrc/nc_piptrack.h kPeakSlots)
 NEAR_TIE = 1e-3    # chroma-lag decisions closer than this (relative xcorr gap) are reported
 TUNING_NEAR_TIE = 1  # tuning decisions whose histogram argmax leads by at most this many residuals
 _logger = logging.getLogger("nightcore_analyzer")
@@ -305,14 +305,58 @@ def _cu_masked_streams(spec: str, num_cu: int, dev: torch.device):
 
 
 @dataclass(eq=False)
-class _TrimBlocks:
-    """A finished (or queued) nc_trim_bounds call: its workspace (the f64 512-sample block sums
-    of files [f0, f1) of the batch), the device offsets of those files and the trim's event."""
+class _Trim:
+    """A queued silence trim of files [f0, f1) of a batch (Engine._trim_launch) and every
+    buffer it owns: the signals, the workspace (the files' f64 512-sample block sums), the files'
+    device offsets, the device bounds and their read-back (pinned, filled by an async copy that
+    ``event`` follows; or None: ``bounds`` copies blocking).  Only ``window_energies`` reads them later."""
+    eng: "Engine"
+    buf: torch.Tensor
     ws: torch.Tensor
     off: "_DevSpan"
     f0: int
     f1: int
+    se: torch.Tensor
+    host: Optional[torch.Tensor]
     event: Optional[torch.cuda.Event]
+
+    def bounds(self) -> Tuple[np.ndarray, np.ndarray]:
+        """Wait for the trim (once) -> (start, end) of files [f0, f1) as fresh int64 arrays."""
+        if self.event is not None:
+            self.event.synchronize()
+            self.event = None
+        elif self.host is None:
+            self.host = self.se.cpu()
+        h, n = self.host.numpy(), self.f1 - self.f0
+        return h[:n].copy(), h[n:].copy()
+
+    def window_energies(self, win_off, win_file, n_win: int, win_n: int, out_ptr: int) -> None:
+        """Queue the block-sum window energies on the current stream: io._rms_db of n_win windows of win_n
+        samples at the absolute offsets win_off, window k in file win_file[k] of this trim.  Records
+        the stream on every device buffer the trim owns: none is reused while the kernel is queued."""
+        s = torch.cuda.current_stream(self.eng.dev)
+        self.eng.call("nc_window_energy_blocks", self.buf.data_ptr(), self.ws.data_ptr(), self.f1 - self.f0,
+                      self.off.data_ptr(), win_off.data_ptr(), win_file.data_ptr(), n_win, win_n, out_ptr,
+                      s.cuda_stream)
+        for t in (self.ws, self.off.base):
+            t.record_stream(s)
+
+
+def window_files(w0, w1, first_file: int = 0) -> np.ndarray:
+    """The file of every window of a plan (BatchPlan.w0 / w1: file f's windows are w0[f]..w1[f])
+    as an int32 index into the trim call that holds the plan's files from ``first_file`` on."""
+    w0a, w1a = np.asarray(w0, np.int64), np.asarray(w1, np.int64)
+    order = np.argsort(w0a, kind="stable")
+    return (np.repeat(order, (w1a - w0a)[order]) + first_file).astype(np.int32)
+
+
+def window_files_by_offset(file_off, win_abs) -> np.ndarray:
+    """``window_files`` from absolute sample offsets alone: the last file that starts at or before
+    each window.  Only right when the files' offsets ascend strictly: ValueError otherwise."""
+    off = np.asarray(file_off, np.int64)
+    if np.any(np.diff(off) <= 0):
+        raise ValueError("file offsets must ascend strictly to look windows up by offset")
+    return (np.searchsorted(off, np.asarray(win_abs, np.int64), side="right") - 1).astype(np.int32)
 
 
 @dataclass(eq=False)
@@ -572,11 +616,27 @@ class _HostViews(dict):
             del self[k]
 
 
+class _StageCopies:
+    """With streamed logs (``on``): copy a group stage's results back as soon as the stage completes (into the places
+    of the arena's pinned mirror the final copy also fills) and keep an event per stage (``ev``)."""
+
+    def __init__(self, ar: _Arena, on: bool):
+        self.ar, self.on, self.ev = ar, on, {}
+
+    def __call__(self, stage: str, stream, parts) -> None:
+        if self.on:
+            with torch.cuda.stream(stream):
+                self.ar.copy_parts(parts)
+                e = torch.cuda.Event()
+                e.record(stream)
+                self.ev[stage] = e
+
+
 class _StageWaiter:
     """wait(stage) for assemble_pair when lines are streamed: emit the pair's lines so far,
-    then wait for that stage's results (engine._launch_group stage_copy)."""
+    then wait for that stage's results (_StageCopies)."""
 
-    def __init__(self, out: PairOutcome, g: dict, h: _HostViews, emit):
+    def __init__(self, out: PairOutcome, g: "_Group", h: _HostViews, emit):
         self.out, self.g, self.h, self.emit = out, g, h, emit
         self.done = 0
 
@@ -588,9 +648,46 @@ class _StageWaiter:
 
     def __call__(self, stage: str) -> None:
         self.flush()
-        ev = self.g["stage_ev"].get(stage) if stage != "final" else None
-        (ev or self.g["event"]).synchronize()
+        ev = self.g.stage_ev.get(stage) if stage != "final" else None
+        (ev or self.g.event).synchronize()
         self.h.refresh()
+
+
+@dataclass(eq=False)
+class _Group:
+    """One launched pair group until the host has assembled it (Engine._launch_group -> _finish_group): its plan,
+    what the final D2H copy fills, the events that say when, every device buffer its kernels use (``keep``)."""
+    pl: BatchPlan
+    p: "Params"
+    align: Optional[list]
+    host: dict                          # {name: numpy view of a pinned buffer} (_Arena.to_host, "ibi_*")
+    arena: tuple                        # _Arena.host_layout
+    pinned: list
+    event: torch.cuda.Event             # after the final copy
+    stage_ev: Dict[str, torch.cuda.Event]   # streamed logs: after each stage's own copy
+    keep: tuple
+    has_ibi: bool
+    nj: int
+    n_pitch_jobs: int
+    spans: Optional[list]               # per pair ((src first sample, length), (nc ...)) for the MELODIA hook
+    bi: int = 0                         # batch, and the group's first pair in it
+    g0: int = 0
+
+
+class _Dims(NamedTuple):
+    """Sizes one group's stages share (Engine._group_upload derives them from the plan)."""
+    T: int              # STFT frames of a window
+    acw: int            # tempogram lags
+    tp: int             # tuning frames of a window's STFT
+    share: bool         # some chunk takes its leading tuning frames from a window's STFT
+    n_shared: int       # tuning frames taken so
+    n_tf: int           # tuning frames of all chunks
+    TV: int             # arena "vals" = [tempo values at the window index (TV) | shift, nc_hz, src_hz (PV)]
+    PV: int
+    nj: int             # bootstrap jobs, seed 42: one per pair (tempo) + n_pitch_jobs (pitch)
+    n_pitch_jobs: int
+    boot_bytes: int     # their workspace, and the chunk-shift bootstrap's
+    shift_bytes: int
 
 
 # ------------------------------------------------------------------------------ engine
@@ -672,6 +769,14 @@ class Engine:
         if v is None:
             v = self._jb_memo[key] = int(self.ctx.lib.nc_bootstrap_job_bytes(cap, n_boot))
         return v
+
+    def _job_offsets(self, caps, n_boot: int = C.N_BOOTSTRAP) -> Tuple[List[int], int]:
+        """(workspace offset of every bootstrap job, total bytes) for jobs of these capacities."""
+        offs, tot = [], 0
+        for c in caps:
+            offs.append(tot)
+            tot += self._job_bytes(int(c), int(n_boot))
+        return offs, tot
 
     def stream(self) -> int:
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -821,10 +926,7 @@ class Engine:
                 vals.append(B)
                 pos += len(B)
             caps.append(len(A) + (len(B) if has_b else 0))
-        wsoff, tot = [], 0
-        for c in caps:
-            wsoff.append(tot)
-            tot += self.ctx.lib.nc_bootstrap_job_bytes(int(c), int(n_boot))
+        wsoff, tot = self._job_offsets(caps, n_boot)
         up = _Upload()
         up.add("vals", np.concatenate(vals) if vals else np.zeros(1), np.float64)
         up.add("a_off", a_off, np.int64)
@@ -891,7 +993,6 @@ class Engine:
                 out.append((p_ * hop_sec, float(speeds[s_])))
         return out
 
-    # -------------------------------------------------------------- batched pipeline
     # -------------------------------------------------------------- spectral (spectral.py:38-103)
     SPECTRAL_BANDS = ((20, 80), (80, 250), (250, 2000), (2000, 6000), (6000, 20000))   # spectral.py:70-74
 
@@ -1015,13 +1116,8 @@ class Engine:
         each stage's results back as the stage completes (energy gate, pitch, source
         tempo, nightcore tempo, consensus), and a pair's lines up to a stage are emitted
         as soon as that stage's results are on the host."""
-        gc_was_enabled = gc.isenabled()
-        gc.disable()
-        try:
+        with _GcPaused():
             return self._analyze(pairs, params, signals, group_pairs, log)
-        finally:
-            if gc_was_enabled:
-                gc.enable()
 
     def analyze_batches(self, batches: Sequence[DeviceSignals], params: Params = None,
                         group_pairs=None) -> List[List[PairOutcome]]:
@@ -1031,21 +1127,13 @@ class Engine:
         still run, so the device does not idle through a batch's start-up (trim read-back,
         host plan of the first group).  Every batch is analysed completely and independently;
         the results equal one ``analyze`` call per batch."""
-        gc_was_enabled = gc.isenabled()
-        gc.disable()
-        try:
+        with _GcPaused():
             return self._analyze_many(list(batches), params or Params(), group_pairs, None)
-        finally:
-            if gc_was_enabled:
-                gc.enable()
 
     def _analyze(self, pairs, params, signals, group_pairs, log=None) -> List[PairOutcome]:
         p = params or Params()
         if signals is None:
-            flat = []
-            for nc, src in pairs:
-                flat += [nc, src]
-            signals = self.upload_signals(flat)
+            signals = self.upload_signals([a for nc, src in pairs for a in (nc, src)])
         return self._analyze_many([signals], p, group_pairs, log)[0]
 
     def _split_trim(self, signals: DeviceSignals, p: Params, groups) -> bool:
@@ -1077,21 +1165,19 @@ class Engine:
         # oldest: the window stream never idles behind the host assembly of an earlier group,
         # the assembly of group g overlaps the device work of the groups after it, and the depth
         # of the device queues (and the memory held by queued groups) stays bounded
-        pending: List[dict] = []
+        pending: List[_Group] = []
 
-        def trim_begin(bi: int, ahead: bool) -> dict:
-            """io.strip_silence bounds of batch bi: two launches when the batch has several
-            groups (the first group's files, then the rest), read back when needed."""
+        def trim_begin(bi: int, ahead: bool) -> Tuple[list, List[_Trim]]:
+            """(pair groups of batch bi, its split trim): io.strip_silence bounds in two launches (the first
+            group's files, then the rest), read back when needed, when the batch has several groups."""
             signals = batches[bi]
             groups = _group_bounds(signals.n_files // 2, group_pairs)
             if not self._split_trim(signals, p, groups):
-                return dict(groups=groups, split=False)
+                return groups, []
             nF, f1 = signals.n_files, 2 * groups[0][1]
-            st0 = self.trim_stream if ahead else launch
-            first = self._trim_launch(signals, 0, f1, p, st0, "trim0", ev_sig)
-            rest = self._trim_launch(signals, f1, nF, p, self.trim_stream if ahead else self.tail_stream, "trim1",
-                                     ev_sig)
-            return dict(groups=groups, split=True, first=first, rest=rest, f1=f1)
+            return groups, [self._trim_launch(signals, 0, f1, p, self.trim_stream if ahead else launch, ev_sig),
+                            self._trim_launch(signals, f1, nF, p, self.trim_stream if ahead else self.tail_stream,
+                                              ev_sig)]
 
         trace = self.host_trace
 
@@ -1099,51 +1185,44 @@ class Engine:
             if trace is not None:
                 trace.append((time.perf_counter(), label))
 
-        def finish(g):
-            mark(f"finish b{g['bi']} g{g['g0']}")
+        def finish(g: _Group):
+            mark(f"finish b{g.bi} g{g.g0}")
             outs = self._finish_group(g, log)
-            results[g["bi"]] += outs
+            results[g.bi] += outs
             if on_group is not None:
-                on_group(g["bi"], g["g0"], outs)
+                on_group(g.bi, g.g0, outs)
 
         nxt = None
         for bi, signals in enumerate(batches):
             t0 = time.perf_counter()
             mark(f"b{bi} trim")
-            tr = nxt if nxt is not None else trim_begin(bi, False)
-            nxt = None
-            groups = tr["groups"]
-            align = None
-            if tr["split"]:
-                nF, f1 = signals.n_files, tr["f1"]
-                start = np.zeros(nF, np.int64)
-                end = np.zeros(nF, np.int64)
-                start[:f1], end[:f1] = self._trim_wait(tr["first"])
-                blocks = [tr["first"][3], tr["rest"][3]]
+            groups, trims = nxt or trim_begin(bi, False)
+            nxt, align, split = None, None, bool(trims)
+            if split:
+                first, rest = trims
+                start, end = np.zeros(signals.n_files, np.int64), np.zeros(signals.n_files, np.int64)
+                start[:first.f1], end[:first.f1] = first.bounds()
             else:
                 start, end, tb = self._trim_all(signals, p)
-                blocks = [tb] if tb is not None else []
+                trims = [tb] if tb is not None else []
                 if p.auto_align and p.src_trim_sec == 0.0:  # pipeline.py:111-125 (manual trim has priority)
                     align = self.align_offsets(signals.buf, signals.off[1::2] + start[1::2], end[1::2] - start[1::2],
                                                signals.off[0::2] + start[0::2], end[0::2] - start[0::2])
             if hs is not None:
                 hs["trim"] = hs.get("trim", 0.0) + time.perf_counter() - t0
             for gi, (g0, g1) in enumerate(groups):
-                if gi == 1 and tr["split"]:
-                    f1 = tr["f1"]
-                    start[f1:], end[f1:] = self._trim_wait(tr["rest"])
+                if gi == 1 and split:
+                    start[rest.f0:], end[rest.f0:] = rest.bounds()
                 sl = slice(2 * g0, 2 * g1)
                 sub = DeviceSignals(signals.buf, signals.off[sl], signals.length[sl])
                 t0 = time.perf_counter()
                 mark(f"b{bi} g{gi} launch")
                 # NC_BLOCK_ENERGY=0 (A/B measurement only): the round-5 per-frame energies in the STFT
-                tb = next((b for b in blocks if b.f0 <= 2 * g0 and 2 * g1 <= b.f1), None) \
+                tb = next((t for t in trims if t.f0 <= 2 * g0 and 2 * g1 <= t.f1), None) \
                     if os.environ.get("NC_BLOCK_ENERGY", "1") != "0" else None
-                g = self._launch_group(sub, p, start[sl].copy(), end[sl].copy(),
-                                       align[g0:g1] if align is not None else None, log is not None,
-                                       blocks=(tb, 2 * g0 - tb.f0) if tb is not None else None)
-                g["g0"], g["bi"] = g0, bi
-                pending.append(g)
+                pending.append(self._launch_group(sub, p, start[sl].copy(), end[sl].copy(),
+                                                  align[g0:g1] if align is not None else None, log is not None,
+                                                  trim=tb, bi=bi, g0=g0))
                 if gi == len(groups) - 1 and bi + 1 < len(batches):
                     mark(f"b{bi + 1} trim_begin")
                     nxt = trim_begin(bi + 1, True)
@@ -1154,7 +1233,7 @@ class Engine:
                     # is complete (or the in-flight cap is reached), so the host's assembly never
                     # leaves the device with just a small group queued
                     while pending and (len(pending) > self.MAX_GROUPS_IN_FLIGHT or
-                                       (len(pending) > 1 and pending[0]["event"].query())):
+                                       (len(pending) > 1 and pending[0].event.query())):
                         finish(pending.pop(0))
                 elif len(pending) > self.GROUPS_IN_FLIGHT:
                     finish(pending.pop(0))
@@ -1165,15 +1244,13 @@ class Engine:
         mark("end")
         return results
 
-    def _trim_launch(self, signals: DeviceSignals, f0: int, f1: int, p: Params, stream, ws_name: str,
-                     ev_sig: Optional[torch.cuda.Event] = None):
-        """Queue nc_trim_bounds for files [f0, f1) on `stream` and the async copy of the bounds
-        into pinned memory; returns (event, pinned bounds, keep-alive).  On a side stream the
-        trim first waits for ev_sig (the signals complete on the launch stream)."""
-        dev = self.dev
-        off, length = signals.off[f0:f1], signals.length[f0:f1]
-        n = f1 - f0
-        lens = np.ascontiguousarray(length, np.int64)
+    def _trim_launch(self, signals: DeviceSignals, f0: int, f1: int, p: Params, stream,
+                     ev_sig: Optional[torch.cuda.Event] = None, pinned: bool = True) -> _Trim:
+        """Queue the silence trim of files [f0, f1) on `stream` and, with ``pinned``, the async copy of
+        the bounds into pinned memory plus an event (else ``_Trim.bounds`` copies them blocking).  On a
+        side stream the trim first waits for ev_sig (the signals complete on the launch stream)."""
+        dev, n = self.dev, f1 - f0
+        lens = np.ascontiguousarray(signals.length[f0:f1], np.int64)
         launch = torch.cuda.current_stream(dev)
         if stream != launch:          # the signals may still be in flight on the launch stream
             if ev_sig is None:
@@ -1182,75 +1259,70 @@ class Engine:
             stream.wait_event(ev_sig)
         with torch.cuda.stream(stream):
             up = _Upload()
-            up.add("off", off, np.int64)
+            up.add("off", signals.off[f0:f1], np.int64)
             up.add("len", lens, np.int64)
             d0 = up.commit(dev, spans=True)
+            # a plain address (ndarray.ctypes.data_as would build a ctypes.cast reference cycle)
             wsb = self.ctx.lib.nc_trim_workspace_bytes(lens.ctypes.data, n)
-            # a fresh workspace per launch (not a named one): its 512-sample block sums give the
-            # batch's window energies later (nc_window_energy_blocks), while the next batch's trim
-            # already runs ahead on the trim stream
+            # a fresh workspace per launch (not a named one): its 512-sample block sums give the batch's window
+            # energies later (_Trim.window_energies), while the next batch's trim already runs ahead
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
             se = torch.empty(2 * n, dtype=torch.int64, device=dev)
             self.call("nc_trim_bounds", signals.buf.data_ptr(), d0["off"].data_ptr(), d0["len"].data_ptr(), n,
                       int(np.sum(1 + lens // 512)), float(p.silence_strip_db), se[:n].data_ptr(),
                       se[n:].data_ptr(), ws.data_ptr(), ws.numel(), stream.cuda_stream)
-            host = torch.empty(2 * n, dtype=torch.int64, pin_memory=True)
-            host.copy_(se, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(stream)
-        return ev, host, (d0, se), _TrimBlocks(ws, d0["off"], f0, f1, ev)
-
-    @staticmethod
-    def _trim_wait(launched) -> Tuple[np.ndarray, np.ndarray]:
-        ev, host, _, _ = launched
-        ev.synchronize()
-        h = host.numpy()
-        n = len(h) // 2
-        return h[:n].copy(), h[n:].copy()
+            host = ev = None
+            if pinned:
+                host = torch.empty(2 * n, dtype=torch.int64, pin_memory=True)
+                host.copy_(se, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(stream)
+        return _Trim(self, signals.buf, ws, d0["off"], f0, f1, se, host, ev)
 
     def _trim_all(self, signals: DeviceSignals, p: Params):
-        """io.strip_silence bounds of every file (sync 1), and the trim's block sums
-        (_TrimBlocks; None without a silence trim)."""
+        """io.strip_silence bounds of every file (sync 1), and the trim that computed them
+        (_Trim; None without a silence trim)."""
         nF = signals.n_files
         if p.silence_strip_db is None:
             return np.zeros(nF, np.int64), signals.length.copy(), None
-        dev, st = self.dev, self.stream()
-        up = _Upload()
-        up.add("off", signals.off, np.int64)
-        up.add("len", signals.length, np.int64)
-        d0 = up.commit(dev)
-        tot_frames = int(np.sum(1 + signals.length // 512))
-        lens = np.ascontiguousarray(signals.length, np.int64)
-        # a plain address (ndarray.ctypes.data_as would build a ctypes.cast reference cycle)
-        wsb = self.ctx.lib.nc_trim_workspace_bytes(lens.ctypes.data, nF)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)     # fresh: its block sums outlive the call
-        se = torch.empty(2 * nF, dtype=torch.int64, device=dev)
-        self.call("nc_trim_bounds", signals.buf.data_ptr(), d0["off"].data_ptr(), d0["len"].data_ptr(), nF,
-                  tot_frames, float(p.silence_strip_db), se[:nF].data_ptr(), se[nF:].data_ptr(),
-                  ws.data_ptr(), ws.numel(), st)
-        se_h = se.cpu().numpy()
-        return se_h[:nF].copy(), se_h[nF:].copy(), _TrimBlocks(ws, d0["off"], 0, nF, None)
+        tb = self._trim_launch(signals, 0, nF, p, torch.cuda.current_stream(self.dev), pinned=False)
+        return (*tb.bounds(), tb)
 
     def _launch_group(self, signals: DeviceSignals, p: Params, start: np.ndarray, end: np.ndarray,
                       align: Optional[List[Tuple[float, float]]] = None, stream_logs: bool = False,
-                      blocks: Optional[Tuple["_TrimBlocks", int]] = None) -> dict:
-        """Queue the whole device pipeline of one group of pairs; returns the pending group.
-        ``blocks``: the silence trim holding this group's files and the index of its first file
-        there; the window energies then come from the trim's block sums, not from the STFT."""
-        dev, st = self.dev, self.stream()
+                      trim: Optional[_Trim] = None, bi: int = 0, g0: int = 0) -> _Group:
+        """Queue the whole device pipeline of one group of pairs (pairs g0.. of batch bi): the chroma
+        chain on stream 2 beside the window/tempo chain on the launch stream, joined by the consensus
+        tail on stream 3; returns the pending group.  ``trim``: the silence trim holding this group's
+        files; the window energies then come from its block sums, not from the STFT."""
         pl = plan_batch(signals.off, signals.length, start, end, p, align)
-        nF, B = pl.nF, pl.B
-        f_off, f_len, strip_len, lead, trail, intro = pl.f_off, pl.f_len, pl.strip_len, pl.lead, pl.trail, pl.intro
-        win_n, hop_n, starts, w0, w1 = pl.win_n, pl.hop_n, pl.starts, pl.w0, pl.w1
-        win_abs, n_win, n_src_w = pl.win_abs, pl.n_win, pl.n_src_w
-        chunk_off, chunk_len, pair_chunks, n_chunks, n_cp = pl.chunk_off, pl.chunk_len, pl.pair_chunks, \
-            pl.n_chunks, pl.n_cp
-        T = 1 + win_n // HOP_LENGTH
-        acw = int(int(8.0 * SR) // HOP_LENGTH)
+        d, dm = self._group_upload(pl, 2 * g0 - trim.f0 if trim is not None else None)
+        ar, o = self._group_arena(pl, dm)
+        stage_copy = _StageCopies(ar, stream_logs)
+        peaks, ev_stft = self._group_plan_ready(dm)
+        onset, tg = self._group_windows(signals, pl, d, o, dm, trim, peaks, ev_stft)
+        ev_chroma = self._group_chroma(signals, pl, d, o, dm, peaks, ev_stft, stage_copy)
+        self._group_tempo(pl, p, d, o, dm, onset, tg, stage_copy)
+        ibi = self._ibi_pass(signals, d["f_off"], d["f_len"], pl.f_len, o["prior"], pl.B, p.ibi_beats) \
+            if p.compute_ibi else None
+        host, pinned, ev = self._group_tail(d, o, dm, ar, ibi, ev_chroma)
+        f_off, f_len = pl.f_off, pl.f_len
+        return _Group(pl=pl, p=p, align=align, host=host, arena=ar.host_layout, pinned=pinned, event=ev,
+                      stage_ev=stage_copy.ev, keep=(d, o, ar, ibi, peaks), has_ibi=ibi is not None, nj=dm.nj,
+                      n_pitch_jobs=dm.n_pitch_jobs, bi=bi, g0=g0,
+                      spans=[((int(f_off[2 * b + 1] - signals.off[2 * b + 1]), int(f_len[2 * b + 1])),
+                              (int(f_off[2 * b] - signals.off[2 * b]), int(f_len[2 * b]))) for b in range(pl.B)]
+                      if p.melodia is not None else None)
 
+    def _group_upload(self, pl: BatchPlan, trim_file: Optional[int]) -> Tuple[dict, _Dims]:
+        """The plan-derived host arrays of one group (window and chunk tables, shared tuning map, bootstrap
+        jobs) in one H2D copy -> (device spans, sizes).  ``trim_file``: its first file within its trim."""
+        B, w0, w1, n_win, n_src_w, f_len = pl.B, pl.w0, pl.w1, pl.n_win, pl.n_src_w, pl.f_len
+        pair_chunks, n_chunks, n_cp = pl.pair_chunks, pl.n_chunks, pl.n_cp
+        T, acw = 1 + pl.win_n // HOP_LENGTH, int(int(8.0 * SR) // HOP_LENGTH)
         # shared tuning frames: a standard 20 s chunk that starts where a window of the same file
         # starts has its first tp tuning frames in that window's STFT (nc_window_stage_tuning)
-        tp = (win_n - 1024) // HOP_LENGTH + 1 if win_n >= 1024 else 0
+        tp = (pl.win_n - 1024) // HOP_LENGTH + 1 if pl.win_n >= 1024 else 0
         share = tp > 0 and n_win > 0 and n_chunks > 0 and self.share_tuning
         win_chunk = np.full(max(1, n_win), -1, np.int32)
         tf_skip = np.zeros(max(1, n_chunks), np.int32)
@@ -1259,116 +1331,73 @@ class Engine:
             share = bool(tf_skip.any())
         chunk_tf_base = np.zeros(max(1, n_chunks) + 1, np.int64)
         if n_chunks:
-            chunk_tf_base[1:n_chunks + 1] = np.cumsum(1 + np.asarray(chunk_len, np.int64) // HOP_LENGTH)
+            chunk_tf_base[1:n_chunks + 1] = np.cumsum(1 + np.asarray(pl.chunk_len, np.int64) // HOP_LENGTH)
 
         # bootstrap jobs (tempo: A = nc valid, B = src valid; pitch: A = nc_hz, B = src_hz; shift)
         n_pitch_jobs = len(pair_chunks)
-        nj = B + n_pitch_jobs
-        TV, PV = max(1, n_win), max(1, 3 * n_cp)   # vals = [tempo values at the window index | shift, nc_hz, src_hz]
+        nj, TV, PV = B + n_pitch_jobs, max(1, n_win), max(1, 3 * n_cp)
         jobs_a_off = [w0[2 * b] for b in range(B)] + [TV + n_cp + c0 for c0, _ in pair_chunks]
         jobs_b_off = [w0[2 * b + 1] for b in range(B)] + [TV + 2 * n_cp + c0 for c0, _ in pair_chunks]
         caps = [max(1, (w1[2 * b] - w0[2 * b]) + (w1[2 * b + 1] - w0[2 * b + 1])) for b in range(B)] + \
                [2 * (c1 - c0) for c0, c1 in pair_chunks]
         p_n = [c1 - c0 for c0, c1 in pair_chunks]
-        jb = self._job_bytes
-        wsoff, tot = [], 0
-        for c in caps:
-            wsoff.append(tot)
-            tot += jb(int(c), C.N_BOOTSTRAP)
-        s_wsoff, s_tot = [], 0
-        for n in p_n:
-            s_wsoff.append(s_tot)
-            s_tot += jb(int(n), C.N_BOOTSTRAP)
-
-        # one H2D copy: plan + bootstrap jobs.  a_n / b_n = [valid counts (written on the
-        # device by nc_collect_valid) | chunk counts of the pitch jobs]
-        up = _Upload()
-        up.add("win_off", win_abs if n_win else [0], np.int64)
-        if blocks is not None and n_win:
-            # each window's file as an index into the trim call that holds the group's files
-            w0a, w1a = np.asarray(w0, np.int64), np.asarray(w1, np.int64)
-            order = np.argsort(w0a, kind="stable")
-            up.add("win_file", np.repeat(order, (w1a - w0a)[order]) + blocks[1], np.int32)
-        up.add("w0", w0, np.int32)
-        up.add("w1", w1, np.int32)
-        up.add("nc_w0", [w0[2 * b] for b in range(B)], np.int32)
-        up.add("nc_w1", [w1[2 * b] for b in range(B)], np.int32)
-        up.add("on_off", np.arange(n_win, dtype=np.int64) * T if n_win else [0], np.int64)
-        up.add("on_len", np.full(max(1, n_win), T), np.int32)
-        up.add("src_w0", [w0[2 * b + 1] for b in range(B)], np.int32)
-        up.add("src_w1", [w1[2 * b + 1] for b in range(B)], np.int32)
-        up.add("src_len", [f_len[2 * b + 1] for b in range(B)], np.int64)
-        up.add("nc_len", [f_len[2 * b] for b in range(B)], np.int64)
-        nc_pair = np.concatenate([np.full(len(starts[2 * b]), b, np.int32) for b in range(B)]) \
+        wsoff, tot = self._job_offsets(caps)
+        s_wsoff, s_tot = self._job_offsets(p_n)
+        nc_pair = np.concatenate([np.full(len(pl.starts[2 * b]), b, np.int32) for b in range(B)]) \
             if n_win - n_src_w else np.zeros(1, np.int32)
-        up.add("nc_pair", nc_pair, np.int32)
-        up.add("src_pair", np.zeros(max(1, n_src_w), np.int32), np.int32)
-        up.add("start120", [120.0], np.float64)
-        up.add("chunk_off", chunk_off or [0], np.int64)
-        up.add("chunk_len", chunk_len or [0], np.int64)
-        up.add("lag_src", np.arange(0, n_chunks, 2), np.int32)
-        up.add("lag_nc", np.arange(1, n_chunks, 2), np.int32)
-        up.add("f_off", f_off, np.int64)
-        up.add("f_len", f_len, np.int64)
-        up.add("a_off", jobs_a_off, np.int64)
-        up.add("b_off", jobs_b_off, np.int64)
-        up.add("a_n", [0] * B + p_n, np.int32)
-        up.add("b_n", [0] * B + p_n, np.int32)
-        up.add("seed", seed_state(42) * nj, np.uint64)
-        up.add("wsoff", wsoff, np.int64)
-        up.add("cap", caps, np.int32)
-        up.add("s_off", [TV + c0 for c0, _ in pair_chunks] or [0], np.int64)
-        up.add("s_n", p_n or [0], np.int32)
-        up.add("s_seed", seed_state(0) * max(1, n_pitch_jobs), np.uint64)
-        up.add("s_wsoff", s_wsoff or [0], np.int64)
-        up.add("s_cap", p_n or [1], np.int32)
-        up.add("win_chunk", win_chunk, np.int32)
-        up.add("tf_skip", tf_skip, np.int32)
-        up.add("tf_base", chunk_tf_base, np.int64)
-        d = up.commit(dev, spans=True)
+        i32, i64, u64 = np.int32, np.int64, np.uint64
+        # each window's file as an index into the trim call that holds the group's files
+        win_file = [("win_file", window_files(w0, w1, trim_file), i32)] if trim_file is not None and n_win else []
+        # a_n / b_n = [valid counts (written on the device by nc_collect_valid) | chunk counts of the pitch jobs]
+        up = _Upload()
+        for name, arr, dt in [("win_off", pl.win_abs if n_win else [0], i64)] + win_file + [
+                ("w0", w0, i32), ("w1", w1, i32), ("nc_w0", w0[0::2], i32), ("nc_w1", w1[0::2], i32),
+                ("on_off", np.arange(n_win, dtype=i64) * T if n_win else [0], i64),
+                ("on_len", np.full(max(1, n_win), T), i32), ("src_w0", w0[1::2], i32), ("src_w1", w1[1::2], i32),
+                ("src_len", f_len[1::2], i64), ("nc_len", f_len[0::2], i64), ("nc_pair", nc_pair, i32),
+                ("src_pair", np.zeros(max(1, n_src_w), i32), i32), ("start120", [120.0], np.float64),
+                ("chunk_off", pl.chunk_off or [0], i64), ("chunk_len", pl.chunk_len or [0], i64),
+                ("lag_src", np.arange(0, n_chunks, 2), i32), ("lag_nc", np.arange(1, n_chunks, 2), i32),
+                ("f_off", pl.f_off, i64), ("f_len", f_len, i64), ("a_off", jobs_a_off, i64), ("b_off", jobs_b_off, i64),
+                ("a_n", [0] * B + p_n, i32), ("b_n", [0] * B + p_n, i32), ("seed", seed_state(42) * nj, u64),
+                ("wsoff", wsoff, i64), ("cap", caps, i32), ("s_off", [TV + c0 for c0, _ in pair_chunks] or [0], i64),
+                ("s_n", p_n or [0], i32), ("s_seed", seed_state(0) * max(1, n_pitch_jobs), u64),
+                ("s_wsoff", s_wsoff or [0], i64), ("s_cap", p_n or [1], i32), ("win_chunk", win_chunk, i32),
+                ("tf_skip", tf_skip, i32), ("tf_base", chunk_tf_base, i64)]:
+            up.add(name, arr, dt)
+        dm = _Dims(T, acw, tp, share, int(tf_skip.sum()), int(chunk_tf_base[n_chunks]), TV, PV, nj, n_pitch_jobs,
+                   tot, s_tot)
+        return up.commit(self.dev, spans=True), dm
 
-        # one zero-filled output arena, copied back in one D2H
+    def _group_arena(self, pl: BatchPlan, dm: _Dims) -> Tuple[_Arena, dict]:
+        """One zero-filled output arena (launch stream), copied back in one D2H."""
+        n_win, n_chunks, n_cp, npj = pl.n_win, pl.n_chunks, pl.n_cp, dm.n_pitch_jobs
         ar = _Arena()
         for name, n, dt in (("chroma", n_chunks * 12, np.float32), ("tuning", n_chunks, np.float32),
-                            ("tmargin", n_chunks, np.int32),
-                            ("clag", n_cp, np.int32), ("cmargin", n_cp, np.float64), ("vals", TV + PV, np.float64), ("energy", n_win, np.float64),
+                            ("tmargin", n_chunks, np.int32), ("clag", n_cp, np.int32), ("cmargin", n_cp, np.float64),
+                            ("vals", dm.TV + dm.PV, np.float64), ("energy", n_win, np.float64),
                             ("active", n_win, np.uint8), ("bpm", n_win, np.float64), ("lag", n_win, np.int32),
-                            ("nbeats", n_win, np.int32), ("margin", n_win, np.float64), ("prior", B, np.float64),
-                            ("bout", 3 * nj, np.float64), ("sout", 3 * max(1, n_pitch_jobs), np.float64),
+                            ("nbeats", n_win, np.int32), ("margin", n_win, np.float64), ("prior", pl.B, np.float64),
+                            ("bout", 3 * dm.nj, np.float64), ("sout", 3 * max(1, npj), np.float64),
                             ("npk", n_chunks, np.int32)):
             ar.add(name, n, dt)
-        o = ar.commit(dev, spans=True)
-        tvals, pvals = o["vals"][:TV], o["vals"][TV:]
+        return ar, ar.commit(self.dev, spans=True)
 
-        # ---------------------------------------------------------------- 3. plan ready -> stream 2
-        # the chroma chain runs on stream 2, concurrently with the window/tempo chain; the
-        # consensus tail joins them.  With shared tuning frames the window stage appends the
-        # leading frames' piptrack peaks to this group's peak lists (its own, zeroed in the
-        # arena) and the chroma chain waits for them before the tuning select.
-        s1, s2 = torch.cuda.current_stream(dev), self.chroma_stream
-        stage_ev: Dict[str, torch.cuda.Event] = {}
-
-        def stage_copy(stage: str, stream, parts) -> None:
-            """With streamed logs: copy a stage's results back as soon as it completes (into
-            the places of the pinned mirror the final copy also fills, before the final
-            copy's stream waits on this one)."""
-            if stream_logs:
-                with torch.cuda.stream(stream):
-                    ar.copy_parts(parts)
-                    e = torch.cuda.Event()
-                    e.record(stream)
-                    stage_ev[stage] = e
-        peaks = None
-        ev_stft = None
-        if share:
+    def _group_plan_ready(self, dm: _Dims):
+        """The plan and the zeroed arena are queued: the chroma stream may start behind them.  With
+        shared tuning frames the window stage appends the leading frames' piptrack peaks to this group's
+        peak lists and the chroma chain waits on ev_stft for them -> (peak lists, ev_stft)."""
+        s1, s2 = torch.cuda.current_stream(self.dev), self.chroma_stream
+        peaks = ev_stft = None
+        if dm.share:
             # peak lists from a ring of GROUPS_IN_FLIGHT + 1 workspaces: a slot comes back only
             # after the host has waited for the group that used it (analyze's in-flight bound),
             # so no large per-group allocation reaches the caching allocator
-            n_slots = int(chunk_tf_base[n_chunks]) * PEAK_SLOTS
+            n_slots = dm.n_tf * PEAK_SLOTS
             ring = max(self.GROUPS_IN_FLIGHT, self.MAX_GROUPS_IN_FLIGHT) + 1
             self._peak_ring = (getattr(self, "_peak_ring", -1) + 1) % ring
             pk = self.workspace(f"peaks{self._peak_ring}", 8 * n_slots)
-            for s_ in (s1, self.chroma_stream):
+            for s_ in (s1, s2):
                 pk.record_stream(s_)
             peaks = (pk[:4 * n_slots].view(torch.float32), pk[4 * n_slots:8 * n_slots].view(torch.float32))
             ev_stft = torch.cuda.Event()
@@ -1376,49 +1405,53 @@ class Engine:
         ev_plan = torch.cuda.Event()
         ev_plan.record(s1)
         s2.wait_event(ev_plan)
+        return peaks, ev_stft
+
+    def _group_windows(self, signals: DeviceSignals, pl: BatchPlan, d, o, dm: _Dims, trim: Optional[_Trim],
+                       peaks, ev_stft):
+        """Per-window stage on the launch stream: energies, onset envelopes, tempogram means
+        (and the shared tuning frames' peaks) -> (onset, tg), or (None, None) without windows."""
+        n_win, win_n = pl.n_win, pl.win_n
+        if not n_win:
+            return None, None
+        dev, st = self.dev, self.stream()
+        onset = torch.empty(n_win * dm.T, dtype=torch.float32, device=dev)
+        tg = torch.empty(n_win * dm.acw, dtype=torch.float64, device=dev)
+        ws = self.workspace("win", self.ctx.lib.nc_window_stage_workspace_bytes(self.ctx.h, n_win, win_n, HOP_LENGTH))
+        # window energies (io._rms_db): from the silence trim's f64 block sums when the batch
+        # was trimmed (the STFT then skips its per-frame energy), else fused into the STFT
+        en_ptr = o["energy"].data_ptr()
+        if trim is not None:
+            trim.window_energies(d["win_off"], d["win_file"], n_win, win_n, en_ptr)
+            en_ptr = None
+        if dm.share:
+            self.call("nc_window_stage_tuning", signals.buf.data_ptr(), d["win_off"].data_ptr(), None, n_win,
+                      win_n, HOP_LENGTH, onset.data_ptr(), tg.data_ptr(), en_ptr,
+                      d["win_chunk"].data_ptr(), d["tf_base"].data_ptr(), dm.tp, peaks[0].data_ptr(),
+                      peaks[1].data_ptr(), o["npk"].data_ptr(), ev_stft.cuda_event, ws.data_ptr(), ws.numel(), st)
+        else:
+            self.call("nc_window_stage", signals.buf.data_ptr(), d["win_off"].data_ptr(), None, n_win, win_n,
+                      HOP_LENGTH, onset.data_ptr(), tg.data_ptr(), en_ptr, ws.data_ptr(), ws.numel(), st)
+        return onset, tg
+
+    def _group_chroma(self, signals: DeviceSignals, pl: BatchPlan, d, o, dm: _Dims, peaks, ev_stft,
+                      stage_copy: "_StageCopies") -> torch.cuda.Event:
+        """The chroma chain on stream 2: chunk chroma and tuning, pair lags, pitch, and the
+        chunk-shift bootstrap (pitch.py:143-150, seed 0), which needs nothing else -> its event."""
+        s2 = self.chroma_stream
         st2 = s2.cuda_stream
-
-        # ---------------------------------------------------------------- 4. per-window stage
-        bpm, lag, nbeats, margin, prior = o["bpm"], o["lag"], o["nbeats"], o["margin"], o["prior"]
-        energy, active = o["energy"], o["active"]
-        if n_win:
-            onset = torch.empty(n_win * T, dtype=torch.float32, device=dev)
-            tg = torch.empty(n_win * acw, dtype=torch.float64, device=dev)
-            wsb = self.ctx.lib.nc_window_stage_workspace_bytes(self.ctx.h, n_win, win_n, HOP_LENGTH)
-            ws = self.workspace("win", wsb)
-            # window energies (io._rms_db): from the silence trim's f64 block sums when the batch
-            # was trimmed (the STFT then skips its per-frame energy), else fused into the STFT
-            en_ptr = energy.data_ptr()
-            if blocks is not None:
-                tb = blocks[0]
-                self.call("nc_window_energy_blocks", signals.buf.data_ptr(), tb.ws.data_ptr(), tb.f1 - tb.f0,
-                          tb.off.data_ptr(), d["win_off"].data_ptr(), d["win_file"].data_ptr(), n_win, win_n,
-                          en_ptr, st)
-                tb.ws.record_stream(torch.cuda.current_stream(dev))
-                en_ptr = None
-            if share:
-                self.call("nc_window_stage_tuning", signals.buf.data_ptr(), d["win_off"].data_ptr(), None, n_win,
-                          win_n, HOP_LENGTH, onset.data_ptr(), tg.data_ptr(), en_ptr,
-                          d["win_chunk"].data_ptr(), d["tf_base"].data_ptr(), tp, peaks[0].data_ptr(),
-                          peaks[1].data_ptr(), o["npk"].data_ptr(), ev_stft.cuda_event, ws.data_ptr(), ws.numel(), st)
-            else:
-                self.call("nc_window_stage", signals.buf.data_ptr(), d["win_off"].data_ptr(), None, n_win, win_n,
-                          HOP_LENGTH, onset.data_ptr(), tg.data_ptr(), en_ptr, ws.data_ptr(), ws.numel(),
-                          st)
-
-        # ---------------------------------------------------------------- 3b. chroma (stream 2)
+        n_chunks, n_cp, chunk_len, npj = pl.n_chunks, pl.n_cp, pl.chunk_len, dm.n_pitch_jobs
+        pvals = o["vals"][dm.TV:]
         if n_chunks:
             tot_len = int(np.sum(chunk_len))
-            wsb = self.ctx.lib.nc_chroma_workspace_bytes(self.ctx.h, n_chunks, tot_len)
-            ws_c = self.workspace("chroma", wsb)
+            ws_c = self.workspace("chroma", self.ctx.lib.nc_chroma_workspace_bytes(self.ctx.h, n_chunks, tot_len))
             ws_c.record_stream(s2)  # used on stream 2: not reusable until that work is done
-            if share:
+            if dm.share:
                 self.call("nc_chroma_mean_shared", signals.buf.data_ptr(), d["chunk_off"].data_ptr(),
                           d["chunk_len"].data_ptr(), n_chunks, tot_len, int(max(chunk_len)), o["chroma"].data_ptr(),
                           o["tuning"].data_ptr(), None, o["tmargin"].data_ptr(), d["tf_skip"].data_ptr(),
-                          int(tf_skip.sum()),
-                          peaks[0].data_ptr(), peaks[1].data_ptr(), o["npk"].data_ptr(), ev_stft.cuda_event,
-                          ws_c.data_ptr(), ws_c.numel(), st2)
+                          dm.n_shared, peaks[0].data_ptr(), peaks[1].data_ptr(), o["npk"].data_ptr(),
+                          ev_stft.cuda_event, ws_c.data_ptr(), ws_c.numel(), st2)
             else:
                 self.call("nc_chroma_mean", signals.buf.data_ptr(), d["chunk_off"].data_ptr(),
                           d["chunk_len"].data_ptr(), n_chunks, tot_len, int(max(chunk_len)), o["chroma"].data_ptr(),
@@ -1427,138 +1460,125 @@ class Engine:
                       d["lag_nc"].data_ptr(), n_cp, o["clag"].data_ptr(), o["cmargin"].data_ptr(), st2)
             self.call("nc_pitch_hz", o["clag"].data_ptr(), n_cp, pvals[0:n_cp].data_ptr(),
                       pvals[n_cp:2 * n_cp].data_ptr(), pvals[2 * n_cp:3 * n_cp].data_ptr(), st2)
-        n_boot = C.N_BOOTSTRAP
-        il, gl, ih, gh = percentile_params(n_boot, C.CI_LEVEL)
-        bout, sout = o["bout"], o["sout"]
-        if n_pitch_jobs:
-            # chunk-shift bootstrap (pitch.py:143-150, seed 0): needs only the chroma chain
-            ws2 = self.workspace("boot_s", s_tot)
+        if npj:
+            sout = o["sout"]
+            ws2 = self.workspace("boot_s", dm.shift_bytes)
             ws2.record_stream(s2)
             self.call("nc_bootstrap_ratio", o["vals"].data_ptr(), d["s_off"].data_ptr(), d["s_n"].data_ptr(), None,
-                      None, n_pitch_jobs, n_boot, d["s_seed"].data_ptr(), il, gl, ih, gh, MIN_CHUNKS,
-                      sout[0:n_pitch_jobs].data_ptr(), sout[n_pitch_jobs:2 * n_pitch_jobs].data_ptr(),
-                      sout[2 * n_pitch_jobs:3 * n_pitch_jobs].data_ptr(), None, d["s_wsoff"].data_ptr(),
-                      d["s_cap"].data_ptr(), ws2.data_ptr(), ws2.numel(), st2)
-        stage_copy("pitch", s2, ["clag", "cmargin", ("vals", TV, TV + PV), "sout", "chroma", "tuning", "tmargin"])
+                      None, npj, C.N_BOOTSTRAP, d["s_seed"].data_ptr(), *_BOOT_PCT, MIN_CHUNKS,
+                      sout[0:npj].data_ptr(), sout[npj:2 * npj].data_ptr(), sout[2 * npj:3 * npj].data_ptr(), None,
+                      d["s_wsoff"].data_ptr(), d["s_cap"].data_ptr(), ws2.data_ptr(), ws2.numel(), st2)
+        stage_copy("pitch", s2, ["clag", "cmargin", ("vals", dm.TV, dm.TV + dm.PV), "sout", "chroma", "tuning",
+                                 "tmargin"])
         ev_chroma = torch.cuda.Event()
         ev_chroma.record(s2)
+        return ev_chroma
 
-        # ---------------------------------------------------------------- 4b. tempo (window stream)
-        # windows longer than ~66 s do not fit the beat tracker's LDS path: global workspace
-        bws, bws_n, btot = None, 0, 0
-        if n_win and beat_needs_workspace(T, acw):
-            wsb = self.workspace("beats", self.ctx.lib.nc_tempo_beats_workspace_bytes(n_win * T))
-            bws, bws_n, btot = wsb.data_ptr(), wsb.numel(), n_win * T
-        if n_win:
-            self.call("nc_energy_gate", energy.data_ptr(), d["w0"].data_ptr(), d["w1"].data_ptr(), nF,
-                      float(p.energy_gate_db), active.data_ptr(), st)
-            stage_copy("gate", s1, ["energy", "active"])
-            if n_src_w:
-                self.call("nc_tempo_beats", onset.data_ptr(), d["on_off"].data_ptr(), d["on_len"].data_ptr(),
-                          n_src_w, T, tg.data_ptr(), acw, d["start120"].data_ptr(), d["src_pair"].data_ptr(),
-                          active.data_ptr(), HOP_LENGTH, 1, bpm.data_ptr(), lag.data_ptr(), nbeats.data_ptr(),
-                          margin.data_ptr(), None, btot, bws, bws_n, st)
-            self.call("nc_tempo_prior", bpm.data_ptr(), nbeats.data_ptr(), active.data_ptr(),
-                      d["src_w0"].data_ptr(), d["src_w1"].data_ptr(), d["src_len"].data_ptr(),
-                      d["nc_len"].data_ptr(), B, prior.data_ptr(), st)
-            stage_copy("src", s1, [("bpm", 0, n_src_w), ("nbeats", 0, n_src_w), ("margin", 0, n_src_w), "prior"])
-            n_nc_w = n_win - n_src_w
-            if n_nc_w:
-                self.call("nc_tempo_beats", onset.data_ptr(),
-                          d["on_off"][n_src_w:].data_ptr(), d["on_len"][n_src_w:].data_ptr(), n_nc_w, T,
-                          tg[n_src_w * acw:].data_ptr(), acw, prior.data_ptr(), d["nc_pair"].data_ptr(),
-                          active[n_src_w:].data_ptr(), HOP_LENGTH, 1, bpm[n_src_w:].data_ptr(),
-                          lag[n_src_w:].data_ptr(), nbeats[n_src_w:].data_ptr(), margin[n_src_w:].data_ptr(),
-                          None, btot, bws, bws_n, st)
-            stage_copy("nc", s1, [("bpm", n_src_w, n_win), ("nbeats", n_src_w, n_win), ("margin", n_src_w, n_win)])
-            # valid-tempo compaction per side: the counts land in the bootstrap jobs' a_n / b_n
-            for side, cnt in (("nc", d["a_n"]), ("src", d["b_n"])):
-                self.call("nc_collect_valid", bpm.data_ptr(), nbeats.data_ptr(), active.data_ptr(),
-                          d[side + "_w0"].data_ptr(), d[side + "_w1"].data_ptr(), B, MIN_BEATS, tvals.data_ptr(),
-                          cnt.data_ptr(), st)
-        else:
+    def _group_tempo(self, pl: BatchPlan, p: Params, d, o, dm: _Dims, onset, tg, stage_copy: "_StageCopies") -> None:
+        """The tempo chain on the launch stream: energy gate, source beats (prior 120), the
+        pairs' priors, nightcore beats, and the valid tempos compacted into the bootstrap jobs."""
+        s1, st = torch.cuda.current_stream(self.dev), self.stream()
+        B, n_win, n_src_w, T, acw = pl.B, pl.n_win, pl.n_src_w, dm.T, dm.acw
+        bpm, lag, nbeats, margin = o["bpm"], o["lag"], o["nbeats"], o["margin"]
+        prior, active, tvals = o["prior"], o["active"], o["vals"][:dm.TV]
+        if not n_win:
             prior.fill_(120.0)
             stage_copy("gate", s1, ["prior"])
+            return
+        # windows longer than ~66 s do not fit the beat tracker's LDS path: global workspace
+        bws, bws_n, btot = None, 0, 0
+        if beat_needs_workspace(T, acw):
+            wsb = self.workspace("beats", self.ctx.lib.nc_tempo_beats_workspace_bytes(n_win * T))
+            bws, bws_n, btot = wsb.data_ptr(), wsb.numel(), n_win * T
+        self.call("nc_energy_gate", o["energy"].data_ptr(), d["w0"].data_ptr(), d["w1"].data_ptr(), pl.nF,
+                  float(p.energy_gate_db), active.data_ptr(), st)
+        stage_copy("gate", s1, ["energy", "active"])
+        if n_src_w:
+            self.call("nc_tempo_beats", onset.data_ptr(), d["on_off"].data_ptr(), d["on_len"].data_ptr(),
+                      n_src_w, T, tg.data_ptr(), acw, d["start120"].data_ptr(), d["src_pair"].data_ptr(),
+                      active.data_ptr(), HOP_LENGTH, 1, bpm.data_ptr(), lag.data_ptr(), nbeats.data_ptr(),
+                      margin.data_ptr(), None, btot, bws, bws_n, st)
+        self.call("nc_tempo_prior", bpm.data_ptr(), nbeats.data_ptr(), active.data_ptr(),
+                  d["src_w0"].data_ptr(), d["src_w1"].data_ptr(), d["src_len"].data_ptr(),
+                  d["nc_len"].data_ptr(), B, prior.data_ptr(), st)
+        stage_copy("src", s1, [("bpm", 0, n_src_w), ("nbeats", 0, n_src_w), ("margin", 0, n_src_w), "prior"])
+        n_nc_w = n_win - n_src_w
+        if n_nc_w:
+            self.call("nc_tempo_beats", onset.data_ptr(),
+                      d["on_off"][n_src_w:].data_ptr(), d["on_len"][n_src_w:].data_ptr(), n_nc_w, T,
+                      tg[n_src_w * acw:].data_ptr(), acw, prior.data_ptr(), d["nc_pair"].data_ptr(),
+                      active[n_src_w:].data_ptr(), HOP_LENGTH, 1, bpm[n_src_w:].data_ptr(),
+                      lag[n_src_w:].data_ptr(), nbeats[n_src_w:].data_ptr(), margin[n_src_w:].data_ptr(),
+                      None, btot, bws, bws_n, st)
+        stage_copy("nc", s1, [("bpm", n_src_w, n_win), ("nbeats", n_src_w, n_win), ("margin", n_src_w, n_win)])
+        # valid-tempo compaction per side: the counts land in the bootstrap jobs' a_n / b_n
+        for side, cnt in (("nc", d["a_n"]), ("src", d["b_n"])):
+            self.call("nc_collect_valid", bpm.data_ptr(), nbeats.data_ptr(), active.data_ptr(),
+                      d[side + "_w0"].data_ptr(), d[side + "_w1"].data_ptr(), B, MIN_BEATS, tvals.data_ptr(),
+                      cnt.data_ptr(), st)
 
-        # ---------------------------------------------------------------- 5. IBI pass (window stream)
-        ibi = None
-        if p.compute_ibi:
-            ibi = self._ibi_pass(signals, d["f_off"], d["f_len"], f_len, prior, B, p.ibi_beats)
+    def _group_tail(self, d, o, dm: _Dims, ar: _Arena, ibi: Optional[dict], ev_chroma: torch.cuda.Event):
+        """The consensus tail on stream 3 once both chains of this group are done (the launch stream
+        is free for the next group's window chain meanwhile): tempo and pitch bootstraps (seed 42), then
+        the async D2H of the arena and the IBI results -> (host views, pinned buffers, final event)."""
         ev_window = torch.cuda.Event()
-        ev_window.record(s1)
-
-        # ---------------------------------------------------------------- 6. bootstraps (tempo + pitch, seed 42)
-        # on the tail stream once both chains of this group are done; the window stream is free
-        # for the next group's window chain meanwhile
+        ev_window.record(torch.cuda.current_stream(self.dev))
         s3 = self.tail_stream
         s3.wait_event(ev_window)
         s3.wait_event(ev_chroma)
-        st3 = s3.cuda_stream
-        ws = self.workspace("boot", tot)
+        nj, bout = dm.nj, o["bout"]
+        ws = self.workspace("boot", dm.boot_bytes)
         ws.record_stream(s3)
         self.call("nc_bootstrap_ratio", o["vals"].data_ptr(), d["a_off"].data_ptr(), d["a_n"].data_ptr(),
-                  d["b_off"].data_ptr(), d["b_n"].data_ptr(), nj, n_boot, d["seed"].data_ptr(), il, gl, ih, gh,
+                  d["b_off"].data_ptr(), d["b_n"].data_ptr(), nj, C.N_BOOTSTRAP, d["seed"].data_ptr(), *_BOOT_PCT,
                   C.MIN_VALID, bout[0:nj].data_ptr(), bout[nj:2 * nj].data_ptr(), bout[2 * nj:].data_ptr(), None,
-                  d["wsoff"].data_ptr(), d["cap"].data_ptr(), ws.data_ptr(), ws.numel(), st3)
-
-        # ---------------------------------------------------------------- 7. async D2H into pinned buffers
+                  d["wsoff"].data_ptr(), d["cap"].data_ptr(), ws.data_ptr(), ws.numel(), s3.cuda_stream)
         with torch.cuda.stream(s3):
             hbuf, host = ar.to_host()
-            host["pvals"] = host["vals"][TV:]
+            host["pvals"] = host["vals"][dm.TV:]
             pinned = [hbuf]
-            if ibi is not None:
-                for k, v in ibi.items():
-                    if isinstance(v, torch.Tensor):
-                        h = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
-                        h.copy_(v, non_blocking=True)
-                        pinned.append(h)
-                        host["ibi_" + k] = h.numpy()
-                    else:
-                        host["ibi_" + k] = v
+            for k, v in (ibi or {}).items():
+                if isinstance(v, torch.Tensor):
+                    h = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
+                    h.copy_(v, non_blocking=True)
+                    pinned.append(h)
+                    host["ibi_" + k] = h.numpy()
+                else:
+                    host["ibi_" + k] = v
             ev = torch.cuda.Event()
             ev.record(s3)
-        return dict(p=p, host=host, arena=ar.host_layout, pinned=pinned, event=ev, stage_ev=stage_ev,
-                    keep=(d, o, ar, ibi, peaks),
-                    has_ibi=ibi is not None,
-                    align=align,
-                    starts=starts, w0=w0, w1=w1, f_len=f_len,
-                    strip_len=strip_len, lead=lead, trail=trail, intro=intro, win_n=win_n,
-                    pair_chunks=pair_chunks, n_cp=n_cp, nj=nj, n_pitch_jobs=n_pitch_jobs, B=B,
-                    spans=[((int(f_off[2 * b + 1] - signals.off[2 * b + 1]), int(f_len[2 * b + 1])),
-                            (int(f_off[2 * b] - signals.off[2 * b]), int(f_len[2 * b]))) for b in range(B)]
-                    if p.melodia is not None else None)
+        return host, pinned, ev
 
-    def _finish_group(self, g: dict, log=None) -> List[PairOutcome]:
+    def _finish_group(self, g: _Group, log=None) -> List[PairOutcome]:
         """Wait for one group's results (sync 2 of that group) and assemble them on the host.
         With ``log``, each pair's lines go out stage by stage as the stages' results land."""
         hs = self.host_stats
         t0 = time.perf_counter()
         if log is None:
-            g["event"].synchronize()
+            g.event.synchronize()
         t1 = time.perf_counter()
         if self.host_trace is not None:
             self.host_trace.append((t1, "synced"))
-        h = _HostViews(g["host"])
+        h = _HostViews(g.host)
         if log is None:
             # group-wide screens (every result is on the host): a pair's own near-tie and beat
             # capacity checks run only when some pair of the group can trip them
             h["any_nb_neg"] = bool((h["nbeats"] < 0).any())
             h["any_cm_tie"] = bool((h["cmargin"] < NEAR_TIE).any())
             h["any_tm_tie"] = bool((h["tmargin"] <= TUNING_NEAR_TIE).any())
-        g["starts_l"] = [x.tolist() for x in g["starts"]]
-        g["w0"], g["w1"] = g["w0"].tolist(), g["w1"].tolist()
-        ibi = {k[4:]: v for k, v in g["host"].items() if k.startswith("ibi_")} if g["has_ibi"] else None
-        ctx = AsmContext(h, ibi, g["starts_l"], g["w0"], g["w1"], g["f_len"], g["strip_len"], g["lead"], g["trail"],
-                         g["intro"], g["win_n"], g["pair_chunks"], g["n_cp"], g["nj"], g["n_pitch_jobs"], g["align"],
-                         g.get("arena"), g["starts"])
+        pl = g.pl
+        ibi = {k[4:]: v for k, v in g.host.items() if k.startswith("ibi_")} if g.has_ibi else None
+        ctx = AsmContext(h=h, ibi=ibi, starts=[x.tolist() for x in pl.starts], w0=pl.w0.tolist(), w1=pl.w1.tolist(),
+                         f_len=pl.f_len, strip_len=pl.strip_len, lead=pl.lead, trail=pl.trail, intro=pl.intro,
+                         win_n=pl.win_n, pair_chunks=pl.pair_chunks, n_cp=pl.n_cp, nj=g.nj,
+                         n_pitch_jobs=g.n_pitch_jobs, align=g.align, arena=g.arena, starts_a=pl.starts)
         out = []
-        for b in range(g["B"]):
+        for b in range(pl.B):
             o = PairOutcome()
             wait = None
             if log is not None:
-                wait = _StageWaiter(o, g, h, lambda line, i=g["g0"] + b: log(i, line))
-            ctx.assemble(b, g["p"], out=o, wait=wait,
-                         span=(g["g0"] + b, g["spans"][b]) if g.get("spans") else None)
+                wait = _StageWaiter(o, g, h, lambda line, i=g.g0 + b: log(i, line))
+            ctx.assemble(b, g.p, out=o, wait=wait, span=(g.g0 + b, g.spans[b]) if g.spans else None)
             if wait is not None:
                 wait.flush()
             out.append(o)
@@ -1619,10 +1639,7 @@ class Engine:
         nb, bpm, lag, mg = core["nbeats"], core["bpm"], core["lag"], core["margin"]
         # bootstrap: A = src ibis, B = nc ibis (consensus.py:303-307), seed 42, need >= 4 each
         caps = [int(frames[2 * b] // 32 + frames[2 * b + 1] // 32 + 4) for b in range(B)]
-        wsoff, tot = [], 0
-        for c in caps:
-            wsoff.append(tot)
-            tot += self.ctx.lib.nc_bootstrap_job_bytes(c, C.N_BOOTSTRAP)
+        wsoff, tot = self._job_offsets(caps)
         up = _Upload()
         up.add("a_off", [fb_h[2 * b + 1] for b in range(B)], np.int64)
         up.add("b_off", [fb_h[2 * b] for b in range(B)], np.int64)

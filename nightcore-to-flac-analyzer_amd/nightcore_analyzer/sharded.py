@@ -80,7 +80,7 @@ import torch.distributed as dist
 from . import consensus as C
 from .distributed import shard_range
 from .engine import (CHUNK_SEC, HOP_LENGTH, IBI_HOP, MIN_BEATS, MIN_CHUNKS, REF_HZ, SR, AsmContext, DeviceSignals,
-                     Engine, PairOutcome, Params, _HostViews, _TrimBlocks, _Upload, plan_batch)
+                     Engine, PairOutcome, Params, _HostViews, _Upload, plan_batch, window_files_by_offset)
 
 # exchanged window record: exists, energy_db, bpm, nbeats, tempo lag, decision margin
 R_EXISTS, R_ENERGY, R_BPM, R_NBEATS, R_LAG, R_MARGIN = range(6)
@@ -766,24 +766,9 @@ class DeviceStages:
 
     def trim(self, p: Params) -> Tuple[np.ndarray, np.ndarray]:
         with torch.cuda.stream(self.stream):
-            eng = self.eng
-            nF = self.sig.n_files
-            up = _Upload()
-            up.add("off", self.off, np.int64)
-            up.add("len", self.length, np.int64)
-            d0 = up.commit(eng.dev)
-            lens = np.ascontiguousarray(self.length, np.int64)
-            # a fresh workspace, kept: its block sums give the window energies (windows()), as
-            # in the engine's pipelined groups
-            ws = torch.empty(eng.ctx.lib.nc_trim_workspace_bytes(lens.ctypes.data, nF), dtype=torch.uint8,
-                             device=eng.dev)
-            se = torch.empty(2 * nF, dtype=torch.int64, device=eng.dev)
-            eng.call("nc_trim_bounds", self.sig.buf.data_ptr(), d0["off"].data_ptr(), d0["len"].data_ptr(), nF,
-                     int(np.sum(1 + lens // 512)), float(p.silence_strip_db), se[:nF].data_ptr(), se[nF:].data_ptr(),
-                     ws.data_ptr(), ws.numel(), eng.stream())
-            self._blocks = _TrimBlocks(ws, d0["off"], 0, nF, None)
-            h = se.cpu().numpy()
-        return h[:nF].copy(), h[nF:].copy()
+            # kept: its block sums give the window energies (windows()), as in the engine's groups
+            self._blocks = self.eng._trim_launch(self.sig, 0, self.sig.n_files, p, self.stream, pinned=False)
+            return self._blocks.bounds()
 
     def align(self, start: np.ndarray, end: np.ndarray) -> List[Tuple[float, float]]:
         o, s = self.sig.off, start
@@ -807,11 +792,9 @@ class DeviceStages:
             ws = eng.workspace("sp_win", eng.ctx.lib.nc_window_stage_workspace_bytes(eng.ctx.h, n, win_n, HOP_LENGTH))
             en_ptr = en.data_ptr()
             tb = self._blocks
-            if tb is not None:          # energies from the trim's block sums (engine._launch_group)
-                wf = np.searchsorted(np.asarray(self.off, np.int64), np.asarray(win_abs, np.int64), side="right") - 1
-                wf_d = torch.from_numpy(wf.astype(np.int32)).to(eng.dev)
-                eng.call("nc_window_energy_blocks", self.sig.buf.data_ptr(), tb.ws.data_ptr(), tb.f1 - tb.f0,
-                         tb.off.data_ptr(), off.data_ptr(), wf_d.data_ptr(), n, win_n, en_ptr, eng.stream())
+            if tb is not None:          # energies from the trim's block sums, as in the engine's groups
+                wf_d = torch.from_numpy(window_files_by_offset(self.off, win_abs)).to(eng.dev)
+                tb.window_energies(off, wf_d, n, win_n, en_ptr)
                 en_ptr = None
             eng.call("nc_window_stage", self.sig.buf.data_ptr(), off.data_ptr(), None, n, win_n, HOP_LENGTH,
                      onset.data_ptr(), tg.data_ptr(), en_ptr, ws.data_ptr(), ws.numel(), eng.stream())

@@ -83,6 +83,73 @@ def test_window_energy_from_trim_blocks(eng):
         assert np.max(np.abs(np.asarray(d) - got[idx])) < 1e-9
 
 
+def test_trim_launch_on_a_side_stream_equals_trim_all(eng):
+    """Engine._trim_launch over files [1, 4) on the trim stream with the pinned asynchronous
+    read-back (the split trim of a multi-group batch) and _trim_all (current stream, blocking
+    copy) give the same bounds for those files, and both the oracle's exactly."""
+    cases = _silence_cases()
+    sig = eng.upload_signals(cases)
+    p = E.Params()
+    tr = eng._trim_launch(sig, 1, 4, p, eng.trim_stream)
+    assert (tr.f0, tr.f1) == (1, 4) and tr.event is not None and tr.host.is_pinned()
+    s1, e1 = tr.bounds()
+    start, end, tb = eng._trim_all(sig, p)
+    assert (tb.f0, tb.f1) == (0, len(cases)) and tb.event is None
+    assert all(a.dtype == np.int64 for a in (s1, e1, start, end))
+    ref = [tuple(int(v) for v in ncref.trim(y, 60.0)[1]) for y in cases]
+    assert list(zip(start.tolist(), end.tolist())) == ref
+    assert list(zip(s1.tolist(), e1.tolist())) == ref[1:4]
+    np.testing.assert_array_equal(s1, start[1:4])
+    np.testing.assert_array_equal(e1, end[1:4])
+    s2, e2 = tr.bounds()                                  # again: the same values, fresh arrays
+    assert s2 is not s1 and s2.tolist() == s1.tolist() and e2.tolist() == e1.tolist()
+
+
+def test_sharded_stages_trim_then_window_energies(eng):
+    """DeviceStages.trim then DeviceStages.windows (the window-sharded run's stages): the
+    energies of every window of a two-pair plan, taken from the trim's block sums with the
+    files looked up by offset, equal io._rms_db of the same samples to 1e-9 dB (the kernel's
+    tolerance in test_window_energy_from_trim_blocks).  One file (40 000 zeros) has no window."""
+    from nightcore_analyzer.sharded import DeviceStages
+    cases = _silence_cases()[:4]
+    sig = eng.upload_signals(cases)
+    p = E.Params(window_sec=2.0, hop_sec=1.0)
+    st = DeviceStages(eng, sig)
+    start, end = st.trim(p)
+    pl = E.plan_batch(sig.off, sig.length, start, end, p)
+    assert pl.n_win > 20 and pl.w0[3] == pl.w1[3]
+    got = st.windows(pl.win_abs, pl.win_n)
+    ref = np.zeros(pl.n_win)
+    for f, y in enumerate(cases):
+        for k in range(pl.w0[f], pl.w1[f]):
+            s = int(pl.win_abs[k] - sig.off[f])
+            ref[k] = refglue.rms_db(y[s:s + pl.win_n])
+    assert got.shape == ref.shape
+    assert np.max(np.abs(got - ref)) < 1e-9
+
+
+def test_small_pipelined_batches_equal_separate_calls(eng):
+    """The small-shape companion of test_gpu_batch.test_pipelined_batches_equal_separate_calls:
+    analyze_batches over three batches of different layouts (3, 1 and 2 pairs of 45 s, 25 s and
+    30 s) in one-pair groups, so the multi-pair batches take the split trim (the next batch's
+    trims queued ahead on the trim stream); every batch's outcomes equal its own analyze call."""
+    from test_gpu_batch import _key
+    p = E.Params(compute_ibi=False)
+    layouts = [(3, 45.0), (1, 25.0), (2, 30.0)]
+    sigs = []
+    for i, (n, sec) in enumerate(layouts):
+        pairs = [synth.make_pair(sec, 1020 + 10 * i + j) for j in range(n)]
+        sigs.append(eng.upload_signals([a for pr in pairs for a in pr]))
+        groups = E._group_bounds(n, 1)
+        assert len(groups) == n and eng._split_trim(sigs[-1], p, groups) == (n > 1)
+    got = eng.analyze_batches(sigs, p, group_pairs=1)
+    assert [len(outs) for outs in got] == [n for n, _ in layouts]
+    for sig, outs in zip(sigs, got):
+        ref = eng.analyze(signals=sig, params=p)
+        assert [_key(o) for o in outs] == [_key(o) for o in ref]
+    assert all(o.error is None for o in got[0])
+
+
 def test_batch_estimate_tempo_and_logs(eng):
     nc, src = synth.make_pair(40.0, 1009)
     wins = nio.slice_windows(nc, 22050)
