@@ -325,7 +325,11 @@ int nc_ibi_tempogram_reduce(nc_ctx* ctx, const double* slab, const int64_t* fram
  * [cand0[w], cand1[w]) whose b positions are pb[item], its a position pa[w]
  * and default exp_pb[w].  Outputs ratio_out[j] (np.polyfit slope) and
  * quality_out[j] (median normalised correlation); (1, 0) with < 3 matches.
- * scratch: dot/sqb = 2 * n_items doubles (caller-owned device memory).
+ * A job may own any number of windows (the reference's n_windows is unbounded).
+ * scratch: dot/sqb = 2 * n_items doubles (caller-owned device memory), holding
+ * nothing of use afterwards: each window's self item must be its own (shared
+ * by no other window or job), because its two slots are reused for that
+ * window's best correlation and b position once its a.a has been read.
  * ------------------------------------------------------------------------- */
 int nc_xcorr_search(nc_ctx* ctx, const float* sig, const int64_t* item_a, const int64_t* item_b,
                     int n_items, int win, double* dot, double* sqb, const int* w0, const int* w1,

@@ -146,6 +146,20 @@ def xcorr_peaks(eng: Engine, src: np.ndarray, nc: np.ndarray) -> List[int]:
     return lag.cpu().numpy()[:n_pairs].astype(int).tolist()
 
 
+def xcorr_geometry(len_a: int, len_b: int, win: int, search: int, stride: int, n_windows: int):
+    """The integer geometry of xcorr.estimate_speed_xcorr's search (xcorr.py:109-125) on the
+    edge-trimmed lengths: [(pa, exp_pb, [candidate pb ...])] for every window with lo < hi."""
+    out = []
+    for pa in np.linspace(0, len_a - win, n_windows).astype(int):
+        pa = int(pa)
+        exp_pb = int(pa * len_b / len_a)
+        lo, hi = max(0, exp_pb - search), min(len_b - win, exp_pb + search)
+        if lo >= hi:
+            continue
+        out.append((pa, exp_pb, list(range(lo, hi, stride))))
+    return out
+
+
 def xcorr_speed(eng: Engine, ya: np.ndarray, yb: np.ndarray, sr: int = SR, n_windows: int = 20,
                 window_sec: float = 3.0, search_range: float = 0.05,
                 skip_edges: float = 0.10) -> Tuple[float, float]:
@@ -161,18 +175,13 @@ def xcorr_speed(eng: Engine, ya: np.ndarray, yb: np.ndarray, sr: int = SR, n_win
     sig = eng.upload_signals([ya, yb])
     oa, ob = int(sig.off[0]), int(sig.off[1])
     ia, ib, sw, c0, c1, pa_l, pb_l, exp_l = [], [], [], [], [], [], [], []
-    for pa in np.linspace(0, len(ya) - win, n_windows).astype(int):
-        pa = int(pa)
-        exp_pb = int(pa * len(yb) / len(ya))
-        lo, hi = max(0, exp_pb - search), min(len(yb) - win, exp_pb + search)
-        if lo >= hi:
-            continue
+    for pa, exp_pb, cands in xcorr_geometry(len(ya), len(yb), win, search, stride, n_windows):
         sw.append(len(ia))
         ia.append(oa + pa)
         ib.append(oa + pa)
         pb_l.append(pa)
         c0.append(len(ia))
-        for pb in range(lo, hi, stride):
+        for pb in cands:
             ia.append(oa + pa)
             ib.append(ob + pb)
             pb_l.append(pb)
