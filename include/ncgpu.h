@@ -446,6 +446,53 @@ int nc_f32_to_pcm16(nc_ctx* ctx, const float* x, const int64_t* in_off, const in
                     void* stream);
 
 /* -------------------------------------------------------------------------
+ * R3  true-peak limiter — replaces the `ffmpeg -af alimiter=limit=L:attack=5:
+ *     release=50:level=disabled` the reference's loudness.apply_true_peak_limiter
+ *     shells out to (loudness.py:86-134), channels linked, no make-up gain.
+ *     PARITY UNPINNED: ffmpeg is not installed and the reference holds no limiter;
+ *     the definition is this project's own (tests/limiter_ref.py).
+ *     For the channels x_c[n], n < N, of one file (zero outside),
+ *     L = 10^(limit_db / 20), Wa = attack, Wr = release (samples), beta = exp(-1 / Wr):
+ *       h(u) = sinc(u) I0(9 sqrt(1 - (u / 12)^2)) / I0(9), |u| < 12,
+ *       x_c(n + k/4) = sum_{i = -11..12} x_c[n + i] h(k/4 - i), k = 1, 2, 3,
+ *       t[n] = max_c max_k |x_c(n + k/4)|, p[n] = max(max_c |x_c[n]|, t[n-1], t[n]),
+ *       r[n] = min(1, L / p[n]) (1 where p = 0 and outside the file),
+ *       hA[n] = min_{0 <= i < Wa} r[n + i], a[n] = (1 / Wa) sum_{0 <= i < Wa} hA[n - i],
+ *       d[n] = max(1 - a[n], beta d[n-1]), d[-1] = 0, g[n] = 1 - d[n],
+ *       y_c[n] = clamp(x_c[n] g[n], -L, L) with L rounded to float.
+ *
+ * A file is a group of consecutive signals of one length (its channels):
+ *     file f = signals file_first[f] .. file_first[f + 1] - 1, file_first[0] = 0
+ *     (device int [n_files + 1]); sig_off / sig_len: device int64 per signal
+ *     (samples).  host_len / host_first are the HOST's copies of sig_len /
+ *     file_first, read by the argument checks and the launch geometry only.
+ *     x (and y) 16-byte aligned.  Files of different lengths and channel counts
+ *     share one call; n_files <= 65535.
+ * nc_limiter_ws_bytes (host only, no context): the workspace bytes of files of
+ *     n_frames[f] frames each, and ws_off[f] (host, nullable) = file f's byte
+ *     offset in it, to be handed to nc_true_peak_limit as a device array.
+ * nc_true_peak: true_peak[f] = max_n p[n] (device float, 0 for an empty file), one
+ *     launch, no workspace.
+ * nc_true_peak_limit: y[y_off[s] + n] for every signal s (y = x with y_off = sig_off
+ *     limits in place), true_peak[f] as above, peak_out[f] = max |y| (device float)
+ *     and limited[f] = #{n : (float)g[n] < 1} (device int), in four launches whatever
+ *     the lengths; no host synchronisation, no allocation; deterministic run to run.
+ *     Returns -2 (nc_last_error) when limit_db > 0, attack outside 1 .. 2048,
+ *     release < 1, a file without channels, channels of unequal length, or a
+ *     workspace below nc_limiter_ws_bytes.  r is computed in f32 (3 x 24 taps), the
+ *     box mean exactly in 64-bit fixed point, the release in f64: g within 1e-4
+ *     of the f64 definition (measured: DESIGN.md §2).
+ * ------------------------------------------------------------------------- */
+size_t nc_limiter_ws_bytes(const int64_t* n_frames, int n_files, int64_t* ws_off);
+int nc_true_peak(nc_ctx* ctx, const float* x, const int64_t* sig_off, const int64_t* sig_len, const int* file_first,
+                 const int64_t* host_len, const int* host_first, int n_files, float* true_peak, void* stream);
+int nc_true_peak_limit(nc_ctx* ctx, const float* x, const int64_t* sig_off, const int64_t* sig_len,
+                       const int* file_first, const int64_t* host_len, const int* host_first, int n_files,
+                       double limit_db, int attack, int release, float* y, const int64_t* y_off, float* true_peak,
+                       float* peak_out, int* limited, void* ws, const int64_t* ws_off, size_t ws_bytes,
+                       void* stream);
+
+/* -------------------------------------------------------------------------
  * MELODIA front end (opt-in; replaces the frame-level part of essentia's
  * PredominantPitchMelodia that pitch.estimate_pitch_melodia calls,
  * pitch.py:210-215: frameSize 2048, hopSize 128).  PARITY UNPINNED: essentia is

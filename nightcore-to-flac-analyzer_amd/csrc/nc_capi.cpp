@@ -105,6 +105,16 @@ int launch_speed_render(Context& ctx, const float* x, const int64_t* in_off, con
 int launch_f32_to_pcm16(const float* x, const int64_t* in_off, const int64_t* in_len, int n_files, int64_t max_len,
                         int16_t* q, const int64_t* out_off, int64_t out_stride, int* clipped, hipStream_t st);
 
+size_t limiter_ws_bytes(const int64_t* n_frames, int n_files, int64_t* ws_off);
+int launch_true_peak(Context& ctx, const float* x, const int64_t* sig_off, const int64_t* sig_len,
+                     const int* file_first, const int64_t* host_len, const int* host_first, int n_files,
+                     float* true_peak, hipStream_t st);
+int launch_true_peak_limit(Context& ctx, const float* x, const int64_t* sig_off, const int64_t* sig_len,
+                           const int* file_first, const int64_t* host_len, const int* host_first, int n_files,
+                           double limit_db, int attack, int release, float* y, const int64_t* y_off,
+                           float* true_peak, float* peak_out, int* limited, void* ws, const int64_t* ws_off,
+                           size_t ws_bytes, hipStream_t st);
+
 int launch_energy_gate(const double* energy, const int* w0, const int* w1, int n_groups, double gate_db,
                        uint8_t* active, hipStream_t st);
 int launch_collect_valid(const double* bpm, const int* nbeats, const uint8_t* active, const int* w0, const int* w1,
@@ -614,6 +624,30 @@ int nc_f32_to_pcm16(nc_ctx* ctx, const float* x, const int64_t* in_off, const in
   SET_DEVICE(ctx);
   return nc::launch_f32_to_pcm16(x, in_off, in_len, n_files, max_len, q, out_off, out_stride, clipped,
                                  (hipStream_t)stream);
+}
+
+size_t nc_limiter_ws_bytes(const int64_t* n_frames, int n_files, int64_t* ws_off) {
+  return nc::limiter_ws_bytes(n_frames, n_files, ws_off);
+}
+
+int nc_true_peak(nc_ctx* ctx, const float* x, const int64_t* sig_off, const int64_t* sig_len, const int* file_first,
+                 const int64_t* host_len, const int* host_first, int n_files, float* true_peak, void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_true_peak(ctx->c, x, sig_off, sig_len, file_first, host_len, host_first, n_files, true_peak,
+                              (hipStream_t)stream);
+}
+
+int nc_true_peak_limit(nc_ctx* ctx, const float* x, const int64_t* sig_off, const int64_t* sig_len,
+                       const int* file_first, const int64_t* host_len, const int* host_first, int n_files,
+                       double limit_db, int attack, int release, float* y, const int64_t* y_off, float* true_peak,
+                       float* peak_out, int* limited, void* ws, const int64_t* ws_off, size_t ws_bytes,
+                       void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_true_peak_limit(ctx->c, x, sig_off, sig_len, file_first, host_len, host_first, n_files, limit_db,
+                                    attack, release, y, y_off, true_peak, peak_out, limited, ws, ws_off, ws_bytes,
+                                    (hipStream_t)stream);
 }
 
 int nc_melodia_salience(nc_ctx* ctx, const float* sig, const int64_t* file_off, const int64_t* file_len,

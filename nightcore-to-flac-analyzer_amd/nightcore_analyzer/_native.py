@@ -81,6 +81,9 @@ SIGNATURES = {
     "nc_speed_out_len": (I32, [D, P, I32, C.POINTER(I64), P]),
     "nc_speed_render": (I32, [P, P, P, P, I32, I64, P, P, I64, P, P]),
     "nc_f32_to_pcm16": (I32, [P, P, P, P, I32, I64, P, P, I64, P, P]),
+    "nc_limiter_ws_bytes": (SZ, [P, I32, P]),
+    "nc_true_peak": (I32, [P, P, P, P, P, P, P, I32, P, P]),
+    "nc_true_peak_limit": (I32, [P, P, P, P, P, P, P, I32, D, I32, I32, P, P, P, P, P, P, P, SZ, P]),
 }
 
 

@@ -43,6 +43,9 @@ def _build_parser() -> argparse.ArgumentParser:
     p.add_argument("--refine", action="store_true",
                    help="With --render-hqnc: re-analyse the render against the nightcore and correct the "
                         "factor until the residual is inside tolerance before writing the file")
+    p.add_argument("--limit", type=float, nargs="?", const=-0.1, default=None, metavar="DB",
+                   help="With --render-hqnc: limit the render to this true-peak ceiling in dBFS on the GPU "
+                        "before it is written (-0.1 when no value is given)")
     return p
 
 
@@ -55,10 +58,13 @@ def _render_hqnc(args, result, nc_path: Path, src_path: Path, log) -> None:
         if log is not None:
             log(f"Refined speed factor: {factor:.6f}× after {ref.corrections} correction(s)"
                 + ("" if ref.converged else "  (not converged)"))
-    info = render.speed_file(src_path, args.render_hqnc, factor)
+    info = render.speed_file(src_path, args.render_hqnc, factor, limit_db=args.limit)
     if log is not None:
         log(f"\nHQNC written to: {info.path}  (speed {info.factor:.6f}×, peak {info.peak_dbfs:+.2f} dBFS, "
             f"{info.clipped_samples} clipped samples)")
+        if info.limit_db is not None:
+            log(f"Limiter at {info.limit_db:+.2f} dBFS: true peak {render._dbfs(info.true_peak):+.2f} dBFS before, "
+                f"peak {info.peak_dbfs:+.2f} dBFS after, {info.limited_samples} samples touched")
 
 
 def output_dict(result) -> dict:
@@ -91,6 +97,10 @@ def main(argv: list[str] | None = None) -> int:
         errors.append("--hop must be less than --window for overlapping windows")
     if args.refine and not args.render_hqnc:
         errors.append("--refine needs --render-hqnc")
+    if args.limit is not None and not args.render_hqnc:
+        errors.append("--limit needs --render-hqnc")
+    if args.limit is not None and not args.limit <= 0.0:
+        errors.append("--limit must be at or below 0 dBFS")
     if errors:
         for e in errors:
             print(f"ERROR: {e}", file=sys.stderr)

@@ -819,6 +819,8 @@ class Engine:
 
     KERNEL_TAGS = ("stft_mel", "window_tg", "tuning_peaks", "decimate", "cqt_low", "cqt_high", "trim_blocks", "tempo_beat",
                    "tg_slide", "spectral_frames", "spectral_bins", "speed_render")
+    # the true-peak limiter's four launches (limiter.hip), read on request: kernel_times(LIMITER_TAGS)
+    LIMITER_TAGS = ("limiter_peak", "limiter_gain", "limiter_carry", "limiter_apply")
 
     def kernel_profile(self, on) -> None:
         """The library's per-kernel timers (nc_profile_enable): False/0 off, True/1 HIP events
@@ -828,10 +830,10 @@ class Engine:
         diagnosis: tools/concurrency_spans.py --marks)."""
         self.ctx.call("nc_profile_enable", int(on))
 
-    def _profile_read(self, fn: str) -> Dict[str, Tuple[float, int]]:
+    def _profile_read(self, fn: str, tags=None) -> Dict[str, Tuple[float, int]]:
         import ctypes as C
         out = {}
-        for tag in self.KERNEL_TAGS:
+        for tag in (self.KERNEL_TAGS if tags is None else tags):
             ms, n = C.c_double(0.0), C.c_int(0)
             self.ctx.call(fn, tag.encode(), C.byref(ms), C.byref(n))
             if n.value:
@@ -842,16 +844,16 @@ class Engine:
             out["cqt_chroma"] = (out["cqt_low"][0] + out["cqt_high"][0], out["cqt_low"][1])
         return out
 
-    def kernel_times(self) -> Dict[str, Tuple[float, int]]:
+    def kernel_times(self, tags=None) -> Dict[str, Tuple[float, int]]:
         """{kernel tag: (total ms, launches)} of the HIP-event brackets since the last read
-        (nc_profile_read); waits for them."""
-        return self._profile_read("nc_profile_read")
+        (nc_profile_read); waits for them.  ``tags``: KERNEL_TAGS unless given."""
+        return self._profile_read("nc_profile_read", tags)
 
-    def kernel_spans(self) -> Dict[str, Tuple[float, int]]:
+    def kernel_spans(self, tags=None) -> Dict[str, Tuple[float, int]]:
         """{kernel tag: (total ms, launches)} of the kernels' execution spans since the last
         read (nc_profile_read_span: first wave start .. last wave end, rocprofv3's kernel
-        duration); waits for them."""
-        return self._profile_read("nc_profile_read_span")
+        duration); waits for them.  ``tags``: KERNEL_TAGS unless given."""
+        return self._profile_read("nc_profile_read_span", tags)
 
     def device_busy(self) -> Tuple[float, float, int]:
         """(busy ms, extent ms, launches) over every kernel span recorded since the last read

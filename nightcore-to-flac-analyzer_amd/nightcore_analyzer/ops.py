@@ -359,3 +359,81 @@ def f32_to_pcm16(eng: Engine, arrays: Sequence[np.ndarray]) -> Tuple[List[np.nda
     q, off, clipped = f32_to_pcm16_device(eng, sig)
     hq = q.cpu().numpy()
     return [hq[o:o + n].copy() for o, n in zip(off, sig.length)], clipped.cpu().numpy()
+
+
+# ------------------------------------------------------------------ true-peak limiter (limiter.hip)
+def limiter_windows(sr: int, attack_ms: float = 5.0, release_ms: float = 50.0) -> Tuple[int, int]:
+    """(Wa, Wr): the limiter's attack and release in samples at rate ``sr``, at least 1 each."""
+    return (max(1, int(round(float(attack_ms) * sr / 1000.0))),
+            max(1, int(round(float(release_ms) * sr / 1000.0))))
+
+
+def _limiter_files(eng: Engine, src, channels):
+    """(DeviceSignals, first[file + 1], host lengths) of ``src`` grouped into files of
+    ``channels`` consecutive signals (an int for every file, or one count per file)."""
+    from .engine import DeviceSignals
+    sig = src if isinstance(src, DeviceSignals) else eng.upload_signals([np.asarray(a, np.float32) for a in src])
+    n_sig = sig.n_files
+    if isinstance(channels, (int, np.integer)):
+        if int(channels) < 1 or n_sig % int(channels):
+            raise ValueError("the signals do not divide into files of that many channels")
+        counts = np.full(n_sig // int(channels), int(channels), np.int64)
+    else:
+        counts = np.asarray(channels, np.int64).reshape(-1)
+    first = np.zeros(len(counts) + 1, np.int32)
+    first[1:] = np.cumsum(counts)
+    if int(first[-1]) != n_sig:
+        raise ValueError("the channel counts do not add up to the number of signals")
+    return sig, first, np.ascontiguousarray(sig.length, np.int64)
+
+
+def true_peak_device(eng: Engine, src, channels=1) -> torch.Tensor:
+    """Inter-sample peak of every file of ``src`` (arrays, or ``DeviceSignals`` already in HBM;
+    a file is ``channels`` consecutive signals of one length): device float32 [file], the
+    limiter's step 1 (``nc_true_peak``).  One launch, no host synchronisation."""
+    sig, first, lens = _limiter_files(eng, src, channels)
+    n = len(first) - 1
+    up = _Upload()
+    up.add("off", sig.off, np.int64)
+    up.add("len", lens, np.int64)
+    up.add("first", first, np.int32)
+    d = up.commit(eng.dev)
+    tp = torch.empty(max(1, n), dtype=torch.float32, device=eng.dev)
+    if n:
+        eng.call("nc_true_peak", sig.buf.data_ptr(), d["off"].data_ptr(), d["len"].data_ptr(), d["first"].data_ptr(),
+                 lens.ctypes.data, first.ctypes.data, n, tp.data_ptr(), eng.stream())
+    return tp[:n]
+
+
+def true_peak_limit_device(eng: Engine, src, channels=1, limit_db: float = -0.1, attack: int = 221,
+                           release: int = 2205, in_place: bool = False):
+    """The linked true-peak limiter (``nc_true_peak_limit``) on every file of
+    ``src`` (arrays, or ``DeviceSignals`` already in HBM; a file is ``channels`` consecutive
+    signals of one length), ceiling ``limit_db`` dBFS, ``attack`` / ``release`` in samples
+    (``limiter_windows``).  Returns (DeviceSignals of the limited signals — ``src``'s own buffer
+    when ``in_place`` —, device float32 true peak in [file], device float32 sample peak out
+    [file], device int32 limited frames [file]).  No host synchronisation."""
+    from . import _native
+    from .engine import DeviceSignals
+    sig, first, lens = _limiter_files(eng, src, channels)
+    n = len(first) - 1
+    frames = np.ascontiguousarray(lens[first[:-1]], np.int64) if n else np.zeros(0, np.int64)
+    ws_off = np.zeros(n, np.int64)
+    nbytes = int(_native.load().nc_limiter_ws_bytes(frames.ctypes.data, n, ws_off.ctypes.data))
+    up = _Upload()
+    up.add("off", sig.off, np.int64)
+    up.add("len", lens, np.int64)
+    up.add("first", first, np.int32)
+    up.add("ws_off", ws_off, np.int64)
+    d = up.commit(eng.dev)
+    out = sig if in_place else DeviceSignals(torch.zeros_like(sig.buf), sig.off, sig.length)
+    tp = torch.empty(max(1, n), dtype=torch.float32, device=eng.dev)[:n]
+    pk = torch.empty(max(1, n), dtype=torch.float32, device=eng.dev)[:n]
+    lim = torch.empty(max(1, n), dtype=torch.int32, device=eng.dev)[:n]
+    if n:
+        ws = eng.workspace("limiter", nbytes)
+        eng.call("nc_true_peak_limit", sig.buf.data_ptr(), d["off"].data_ptr(), d["len"].data_ptr(),
+                 d["first"].data_ptr(), lens.ctypes.data, first.ctypes.data, n, float(limit_db), int(attack),
+                 int(release), out.buf.data_ptr(), d["off"].data_ptr(), tp.data_ptr(), pk.data_ptr(), lim.data_ptr(),
+                 ws.data_ptr(), d["ws_off"].data_ptr(), ws.numel(), eng.stream())
+    return out, tp, pk, lim

@@ -8,7 +8,8 @@ renderer's definition is this project's own (``nc_speed_render`` in
 include/ncgpu.h): a Kaiser-windowed sinc (beta 10.06, 32 zero crossings a side, cut-off at
 0.9 of the lower Nyquist) evaluated at the exact rational position m P / 10^6 of every output.
 
-* ``speed`` / ``speed_file`` — the render of an array / of every channel of a WAV file.
+* ``speed`` / ``speed_file`` — the render of an array / of every channel of a WAV file
+  (``limit_db``: with the true-peak limiter on the resident render, loudness.py).
 * ``refine_speed`` — render, re-analyse, correct; the render stays in HBM between the two.
 * ``quantize_factor`` / ``hqnc_path`` — the six-decimal factor and the output naming rule.
 """
@@ -62,6 +63,10 @@ class RenderInfo:
     peak: float                # max |sample| over all channels, before any 16-bit clamp
     peak_dbfs: float
     clipped_samples: int       # samples at or beyond full scale (clamped, in a 16-bit file)
+    # with ``speed_file(limit_db=...)``: ``peak`` / ``clipped_samples`` describe the limited file
+    true_peak: Optional[float] = None      # inter-sample peak of the render before the limiter
+    limited_samples: int = 0               # frames the limiter turned down
+    limit_db: Optional[float] = None       # the ceiling, dBFS
 
     @property
     def is_clipping(self) -> bool:
@@ -79,17 +84,28 @@ def speed(y: np.ndarray, factor: float, sr: Optional[int] = None) -> np.ndarray:
     return out
 
 
-def speed_file(src_path, dst_path, factor: float) -> RenderInfo:
+def speed_file(src_path, dst_path, factor: float, limit_db: Optional[float] = None, *,
+               attack_ms: float = 5.0, release_ms: float = 50.0) -> RenderInfo:
     """Render every channel of the WAV file ``src_path`` at its own rate and write
     ``dst_path``: a 16-bit PCM source gives a 16-bit PCM file (quantised on the device,
-    ``nc_f32_to_pcm16``), anything else a float32 file."""
+    ``nc_f32_to_pcm16``), anything else a float32 file.  With a ceiling ``limit_db`` (dBFS,
+    at most 0) the true-peak limiter (``nc_true_peak_limit``, channels linked) runs on the
+    resident render before the quantisation; the render does not leave HBM in between."""
     from .engine import get_engine
-    from .ops import f32_to_pcm16_device, speed_render_device
+    from .ops import f32_to_pcm16_device, limiter_windows, speed_render_device, true_peak_limit_device
     f = quantize_factor(factor)
+    if limit_db is not None and not float(limit_db) <= 0.0:
+        raise ValueError(f"limiter ceiling {limit_db!r} dBFS is above full scale")
     data, sr, fmt = read_wav_channels(src_path)
     eng = get_engine()
     out, peak_d, P = speed_render_device(eng, list(data), f)
     ch, n_out = data.shape[0], int(out.length[0])
+    extra = {}
+    if limit_db is not None and ch:
+        wa, wr = limiter_windows(sr, attack_ms, release_ms)
+        out, tp_d, pk_d, lim_d = true_peak_limit_device(eng, out, ch, float(limit_db), wa, wr, in_place=True)
+        peak_d = pk_d
+        extra = dict(true_peak=tp_d, limited_samples=lim_d, limit_db=float(limit_db))
     if fmt == "pcm16":
         q, _, clipped_d = f32_to_pcm16_device(eng, out, interleave=True)
         frames = q[:ch * n_out].cpu().numpy().reshape(n_out, ch).T
@@ -102,7 +118,10 @@ def speed_file(src_path, dst_path, factor: float) -> RenderInfo:
         out_fmt = "float32"
     write_wav(dst_path, frames, sr, out_fmt)
     peak = float(peak_d.max().item()) if ch else 0.0
-    return RenderInfo(Path(dst_path), P / Q, n_out, ch, sr, out_fmt, peak, _dbfs(peak), clipped)
+    if extra:
+        extra.update(true_peak=float(extra["true_peak"][0].item()),
+                     limited_samples=int(extra["limited_samples"][0].item()))
+    return RenderInfo(Path(dst_path), P / Q, n_out, ch, sr, out_fmt, peak, _dbfs(peak), clipped, **extra)
 
 
 @dataclass
