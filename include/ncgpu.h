@@ -493,6 +493,71 @@ int nc_true_peak_limit(nc_ctx* ctx, const float* x, const int64_t* sig_off, cons
                        void* stream);
 
 /* -------------------------------------------------------------------------
+ * R4  phase-vocoder time stretch — with nc_speed_render at the same ratio it
+ *     replaces the `rubberband --pitch S` the reference's workflow shells out to
+ *     (workflow.py:121-131): a pitch shift by S semitones, duration kept.
+ *     PARITY UNPINNED: rubberband is not installed and the reference holds no
+ *     pitch shifter; the definition is this project's own (DESIGN.md §4,
+ *     tests/pvoc_ref.py).  Plain phase vocoder: no transient detection, no phase
+ *     locking, channels independent.  N = 2048, Hs = 512, Q = 1e6,
+ *     W[j] = 0.5 - 0.5 cos(2 pi j / N), P = round(2^(S/12) Q), |S| <= 12; for one
+ *     channel x[0..n) (zero outside), every integer division a floor division:
+ *       Ns = ceil(n P / Q), K = ceil(Ns / Hs) + 3 (0 when n = 0),
+ *       u_k = ((k - 1) Hs Q) div P,
+ *       A_k = rfft(x[u_k - N/2 + i] W[i]), B_k = the frame Hs samples earlier,
+ *       mag_k = |A_k|, empty_k = every x[i], u_k - N/2 < i < u_k + N/2, is +-0,
+ *       reset_k = (k == 0) or empty_{k-1}, ph(z) = z / |z|, (1, 0) at |z| = 0 / inf,
+ *       V_k = ph(A_k) on a reset frame, else ph(A_k conj(B_k)),
+ *       Phi_k = V_k on a reset frame, else ph(Phi_{k-1} V_k),
+ *       f_k[i] = irfft(mag_k Phi_k)[i] W[i] 2/3,
+ *       s[m] = sum_{k = j..j+3} f_k[m - (k - 3) Hs], j = m div Hs, m < Ns (ascending k).
+ *     The shifted signal is nc_speed_render(s, p = P)[0..n).
+ *
+ * Frames of all files are numbered consecutively: frame g = frame_base[f] + k.
+ *     mag: device float [total_frames][1025]; v / phi: device float
+ *     [total_frames][1025][2] (re, im); empty: device uint8 [total_frames];
+ *     in_off / in_len / out_off: device int64 [n_files] (samples); frame_base:
+ *     device int64 [n_files + 1].  Files of different lengths share one call,
+ *     n_files <= 65535, n = 0 is legal (no frames, peak 0).  Every entry returns -2
+ *     (nc_last_error) on an argument error; none allocates or synchronises the
+ *     host; every sum runs in a fixed order: bit-identical run to run and batch
+ *     to single.
+ * nc_pv_plan (host only, no context): for p = P and n_files host lengths,
+ *     ns_out[f] = Ns, k_out[f] = K, frame_base[f] (host, [n_files + 1]: to be
+ *     handed on as a device array), and the workspace of nc_pv_stretch:
+ *     ws_off[0..5] = byte offsets of mag, v, phi, the frame buffer
+ *     ([total_frames][2048] float), empty and the scan workspace, *ws_bytes the
+ *     total.  Every output is nullable.  -2 outside 500000 <= p <= 2000000.
+ * nc_pv_analyze: mag, v and empty of every frame (one launch).
+ * nc_pv_scan: phi from v and empty (three launches: tiles of 64 frames multiplied
+ *     up in f64, the carries over the tile aggregates, the apply pass).
+ *     max_frames = the largest K; ws: at least nc_pv_scan_ws_bytes(total_frames,
+ *     n_files) bytes (host only; the region nc_pv_plan puts at ws_off[5]), 16-byte
+ *     aligned.
+ * nc_pv_synth: s[out_off[f] + m], m < Ns(in_len[f]), and peak[f] = max_m |s[m]|
+ *     (device float, 0 for an empty file) from mag and phi (two launches: the
+ *     windowed inverse FFTs into `frames`, frames_bytes >= 8192 total_frames, then
+ *     the four-frame gather).  max_ns = the largest Ns.
+ * nc_pv_stretch: the three stages over one workspace laid out by nc_pv_plan
+ *     (ws_off: the HOST array nc_pv_plan filled), six launches whatever the lengths.
+ * ------------------------------------------------------------------------- */
+int nc_pv_plan(int64_t p, const int64_t* n_in, int n_files, int64_t* ns_out, int64_t* k_out, int64_t* frame_base,
+               int64_t* ws_off, size_t* ws_bytes);
+size_t nc_pv_scan_ws_bytes(int64_t total_frames, int n_files);
+int nc_pv_analyze(nc_ctx* ctx, const float* x, const int64_t* in_off, const int64_t* in_len,
+                  const int64_t* frame_base, int n_files, int64_t total_frames, int64_t p, float* mag, float* v,
+                  uint8_t* empty, void* stream);
+int nc_pv_scan(nc_ctx* ctx, const float* v, const uint8_t* empty, const int64_t* frame_base, int n_files,
+               int64_t total_frames, int64_t max_frames, float* phi, void* ws, size_t ws_bytes, void* stream);
+int nc_pv_synth(nc_ctx* ctx, const float* mag, const float* phi, const int64_t* in_len, const int64_t* frame_base,
+                int n_files, int64_t total_frames, int64_t p, int64_t max_ns, void* frames, size_t frames_bytes,
+                float* s, const int64_t* out_off, float* peak, void* stream);
+int nc_pv_stretch(nc_ctx* ctx, const float* x, const int64_t* in_off, const int64_t* in_len,
+                  const int64_t* frame_base, int n_files, int64_t total_frames, int64_t max_frames, int64_t p,
+                  int64_t max_ns, float* s, const int64_t* out_off, float* peak, void* ws, const int64_t* ws_off,
+                  size_t ws_bytes, void* stream);
+
+/* -------------------------------------------------------------------------
  * MELODIA front end (opt-in; replaces the frame-level part of essentia's
  * PredominantPitchMelodia that pitch.estimate_pitch_melodia calls,
  * pitch.py:210-215: frameSize 2048, hopSize 128).  PARITY UNPINNED: essentia is

@@ -115,6 +115,19 @@ int launch_true_peak_limit(Context& ctx, const float* x, const int64_t* sig_off,
                            float* true_peak, float* peak_out, int* limited, void* ws, const int64_t* ws_off,
                            size_t ws_bytes, hipStream_t st);
 
+int pv_plan(int64_t P, const int64_t* n_in, int n_files, int64_t* ns_out, int64_t* k_out, int64_t* frame_base,
+            int64_t* ws_off, size_t* ws_bytes);
+size_t pv_scan_ws_bytes(int64_t total_frames, int n_files);
+int launch_pv_analyze(Context& ctx, const float* x, const int64_t* in_off, const int64_t* in_len,
+                      const int64_t* frame_base, int n_files, int64_t total_frames, int64_t P, float* mag, float2* V,
+                      uint8_t* empty, hipStream_t st);
+int launch_pv_scan(Context& ctx, const float2* V, const uint8_t* empty, const int64_t* frame_base, int n_files,
+                   int64_t total_frames, int64_t max_frames, float2* phi, void* ws, size_t ws_bytes, hipStream_t st);
+int launch_pv_synth(Context& ctx, const float* mag, const float2* phi, const int64_t* in_len,
+                    const int64_t* frame_base, int n_files, int64_t total_frames, int64_t P, int64_t max_ns,
+                    float* frames, size_t frames_bytes, float* s, const int64_t* out_off, float* peak,
+                    hipStream_t st);
+
 int launch_energy_gate(const double* energy, const int* w0, const int* w1, int n_groups, double gate_db,
                        uint8_t* active, hipStream_t st);
 int launch_collect_valid(const double* bpm, const int* nbeats, const uint8_t* active, const int* w0, const int* w1,
@@ -648,6 +661,86 @@ int nc_true_peak_limit(nc_ctx* ctx, const float* x, const int64_t* sig_off, cons
   return nc::launch_true_peak_limit(ctx->c, x, sig_off, sig_len, file_first, host_len, host_first, n_files, limit_db,
                                     attack, release, y, y_off, true_peak, peak_out, limited, ws, ws_off, ws_bytes,
                                     (hipStream_t)stream);
+}
+
+int nc_pv_plan(int64_t p, const int64_t* n_in, int n_files, int64_t* ns_out, int64_t* k_out, int64_t* frame_base,
+               int64_t* ws_off, size_t* ws_bytes) {
+  return nc::pv_plan(p, n_in, n_files, ns_out, k_out, frame_base, ws_off, ws_bytes);
+}
+
+size_t nc_pv_scan_ws_bytes(int64_t total_frames, int n_files) {
+  return total_frames < 0 || n_files < 0 ? 0 : nc::pv_scan_ws_bytes(total_frames, n_files);
+}
+
+int nc_pv_analyze(nc_ctx* ctx, const float* x, const int64_t* in_off, const int64_t* in_len,
+                  const int64_t* frame_base, int n_files, int64_t total_frames, int64_t p, float* mag, float* v,
+                  uint8_t* empty, void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_pv_analyze(ctx->c, x, in_off, in_len, frame_base, n_files, total_frames, p, mag,
+                               reinterpret_cast<float2*>(v), empty, (hipStream_t)stream);
+}
+
+int nc_pv_scan(nc_ctx* ctx, const float* v, const uint8_t* empty, const int64_t* frame_base, int n_files,
+               int64_t total_frames, int64_t max_frames, float* phi, void* ws, size_t ws_bytes, void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_pv_scan(ctx->c, reinterpret_cast<const float2*>(v), empty, frame_base, n_files, total_frames,
+                            max_frames, reinterpret_cast<float2*>(phi), ws, ws_bytes, (hipStream_t)stream);
+}
+
+int nc_pv_synth(nc_ctx* ctx, const float* mag, const float* phi, const int64_t* in_len, const int64_t* frame_base,
+                int n_files, int64_t total_frames, int64_t p, int64_t max_ns, void* frames, size_t frames_bytes,
+                float* s, const int64_t* out_off, float* peak, void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_pv_synth(ctx->c, mag, reinterpret_cast<const float2*>(phi), in_len, frame_base, n_files,
+                             total_frames, p, max_ns, static_cast<float*>(frames), frames_bytes, s, out_off, peak,
+                             (hipStream_t)stream);
+}
+
+int nc_pv_stretch(nc_ctx* ctx, const float* x, const int64_t* in_off, const int64_t* in_len,
+                  const int64_t* frame_base, int n_files, int64_t total_frames, int64_t max_frames, int64_t p,
+                  int64_t max_ns, float* s, const int64_t* out_off, float* peak, void* ws, const int64_t* ws_off,
+                  size_t ws_bytes, void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  if (n_files < 0 || total_frames < 0) {
+    nc::set_error("nc_pv_stretch: negative file or frame count");
+    return -2;
+  }
+  const size_t t = (size_t)total_frames;
+  const size_t need[6] = {t * 1025 * sizeof(float), t * 1025 * 2 * sizeof(float), t * 1025 * 2 * sizeof(float),
+                          t * 2048 * sizeof(float), t, nc::pv_scan_ws_bytes(total_frames, std::max(0, n_files))};
+  char* w = static_cast<char*>(ws);
+  if (total_frames > 0) {
+    if (!ws || !ws_off) {
+      nc::set_error("nc_pv_stretch: null workspace");
+      return -2;
+    }
+    for (int i = 0; i < 6; ++i) {
+      const int64_t end = i + 1 < 6 ? ws_off[i + 1] : (int64_t)ws_bytes;
+      if (ws_off[i] < 0 || (ws_off[i] & 15) || end < ws_off[i] || (size_t)(end - ws_off[i]) < need[i] ||
+          (size_t)end > ws_bytes) {
+        nc::set_error("nc_pv_stretch: workspace below nc_pv_plan's layout");
+        return -2;
+      }
+    }
+  }
+  float* mag = total_frames > 0 ? reinterpret_cast<float*>(w + ws_off[0]) : nullptr;
+  float2* v = total_frames > 0 ? reinterpret_cast<float2*>(w + ws_off[1]) : nullptr;
+  float2* phi = total_frames > 0 ? reinterpret_cast<float2*>(w + ws_off[2]) : nullptr;
+  float* frames = total_frames > 0 ? reinterpret_cast<float*>(w + ws_off[3]) : nullptr;
+  uint8_t* empty = total_frames > 0 ? reinterpret_cast<uint8_t*>(w + ws_off[4]) : nullptr;
+  void* scan_ws = total_frames > 0 ? static_cast<void*>(w + ws_off[5]) : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = nc::launch_pv_analyze(ctx->c, x, in_off, in_len, frame_base, n_files, total_frames, p, mag, v, empty, st);
+  if (rc) return rc;
+  rc = nc::launch_pv_scan(ctx->c, v, empty, frame_base, n_files, total_frames, max_frames, phi, scan_ws,
+                          total_frames > 0 ? ws_bytes - (size_t)ws_off[5] : 0, st);
+  if (rc) return rc;
+  return nc::launch_pv_synth(ctx->c, mag, phi, in_len, frame_base, n_files, total_frames, p, max_ns, frames,
+                             need[3], s, out_off, peak, st);
 }
 
 int nc_melodia_salience(nc_ctx* ctx, const float* sig, const int64_t* file_off, const int64_t* file_len,

@@ -84,6 +84,12 @@ SIGNATURES = {
     "nc_limiter_ws_bytes": (SZ, [P, I32, P]),
     "nc_true_peak": (I32, [P, P, P, P, P, P, P, I32, P, P]),
     "nc_true_peak_limit": (I32, [P, P, P, P, P, P, P, I32, D, I32, I32, P, P, P, P, P, P, P, SZ, P]),
+    "nc_pv_plan": (I32, [I64, P, I32, P, P, P, P, C.POINTER(SZ)]),
+    "nc_pv_scan_ws_bytes": (SZ, [I64, I32]),
+    "nc_pv_analyze":(I32, [P, P, P, P, P, I32, I64, I64, P, P, P, P]),
+    "nc_pv_scan": (I32, [P, P, P, P, I32, I64, I64, P, P, SZ, P]),
+    "nc_pv_synth": (I32, [P, P, P, P, P, I32, I64, I64, I64, P, SZ, P, P, P, P]),
+    "nc_pv_stretch": (I32, [P, P, P, P, P, I32, I64, I64, I64, I64, P, P, P, P, P, SZ, P]),
 }
 
 

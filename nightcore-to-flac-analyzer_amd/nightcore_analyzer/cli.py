@@ -45,8 +45,24 @@ def _build_parser() -> argparse.ArgumentParser:
                         "factor until the residual is inside tolerance before writing the file")
     p.add_argument("--limit", type=float, nargs="?", const=-0.1, default=None, metavar="DB",
                    help="With --render-hqnc: limit the render to this true-peak ceiling in dBFS on the GPU "
-                        "before it is written (-0.1 when no value is given)")
+                        "before it is written (-0.1 when no value is given); applies to --pitch-correct too")
+    p.add_argument("--pitch-correct", metavar="OUT.wav", default=None,
+                   help="After the analysis, write the source shifted in pitch by --semitones (duration kept) "
+                        "to this WAV file on the GPU")
+    p.add_argument("--semitones", type=float, default=None, metavar="S",
+                   help="With --pitch-correct: the shift in semitones (-12 .. 12)")
     return p
+
+
+def _pitch_correct(args, src_path: Path, log) -> None:
+    from . import render
+    info = render.pitch_file(src_path, args.pitch_correct, args.semitones, limit_db=args.limit)
+    if log is not None:
+        log(f"\nPitch-corrected file written to: {info.path}  (pitch {info.semitones:+.6f} st, ratio "
+            f"{info.factor:.6f}, peak {info.peak_dbfs:+.2f} dBFS, {info.clipped_samples} clipped samples)")
+        if info.limit_db is not None:
+            log(f"Limiter at {info.limit_db:+.2f} dBFS: true peak {render._dbfs(info.true_peak):+.2f} dBFS before, "
+                f"peak {info.peak_dbfs:+.2f} dBFS after, {info.limited_samples} samples touched")
 
 
 def _render_hqnc(args, result, nc_path: Path, src_path: Path, log) -> None:
@@ -97,8 +113,14 @@ def main(argv: list[str] | None = None) -> int:
         errors.append("--hop must be less than --window for overlapping windows")
     if args.refine and not args.render_hqnc:
         errors.append("--refine needs --render-hqnc")
-    if args.limit is not None and not args.render_hqnc:
-        errors.append("--limit needs --render-hqnc")
+    if args.limit is not None and not args.render_hqnc and not args.pitch_correct:
+        errors.append("--limit needs --render-hqnc or --pitch-correct")
+    if args.pitch_correct and args.semitones is None:
+        errors.append("--pitch-correct needs --semitones")
+    if args.semitones is not None and not args.pitch_correct:
+        errors.append("--semitones needs --pitch-correct")
+    if args.semitones is not None and not abs(args.semitones) <= 12.0:
+        errors.append("--semitones must be within -12 .. 12")
     if args.limit is not None and not args.limit <= 0.0:
         errors.append("--limit must be at or below 0 dBFS")
     if errors:
@@ -130,6 +152,12 @@ def main(argv: list[str] | None = None) -> int:
     if args.render_hqnc:
         try:
             _render_hqnc(args, result, nc_path, src_path, log)
+        except Exception as exc:
+            print(f"\nERROR: {exc}", file=sys.stderr)
+            return 1
+    if args.pitch_correct:
+        try:
+            _pitch_correct(args, src_path, log)
         except Exception as exc:
             print(f"\nERROR: {exc}", file=sys.stderr)
             return 1

@@ -821,6 +821,8 @@ class Engine:
                    "tg_slide", "spectral_frames", "spectral_bins", "speed_render")
     # the true-peak limiter's four launches (limiter.hip), read on request: kernel_times(LIMITER_TAGS)
     LIMITER_TAGS = ("limiter_peak", "limiter_gain", "limiter_carry", "limiter_apply")
+    # the phase-vocoder stretch's six launches (pvoc.hip), read on request: kernel_times(PV_TAGS)
+    PV_TAGS = ("pv_analysis", "pv_scan_tile", "pv_scan_carry", "pv_scan_apply", "pv_synth", "pv_ola")
 
     def kernel_profile(self, on) -> None:
         """The library's per-kernel timers (nc_profile_enable): False/0 off, True/1 HIP events

@@ -75,6 +75,12 @@ class DeviceAudio:
     def numpy(self) -> np.ndarray:
         return self.tensor.cpu().numpy()
 
+    def __getitem__(self, key) -> "DeviceAudio":
+        """A slice of the signal, still in HBM (the 20 s chunks of the pitch estimate)."""
+        if not isinstance(key, slice):
+            raise TypeError("DeviceAudio supports slices only")
+        return DeviceAudio(self.tensor.reshape(-1)[key], self.sr)
+
 
 def as_f32(a) -> np.ndarray:
     """The float32 samples of ``a``: a Pcm16 scaled by 1 / 32768, anything else as float32."""

@@ -437,3 +437,169 @@ def true_peak_limit_device(eng: Engine, src, channels=1, limit_db: float = -0.1,
                  int(release), out.buf.data_ptr(), d["off"].data_ptr(), tp.data_ptr(), pk.data_ptr(), lim.data_ptr(),
                  ws.data_ptr(), d["ws_off"].data_ptr(), ws.numel(), eng.stream())
     return out, tp, pk, lim
+
+
+# ------------------------------------------------------------------ pitch shift (pvoc.hip + speed.hip)
+PV_Q = 1_000_000
+PV_BINS = 1025
+PV_N = 2048
+PV_TILE = 64             # frames per tile of the phase scan (pvoc.hip PV_TILE)
+MAX_SEMITONES = 12.0
+
+
+def pitch_p(semitones: float) -> int:
+    """P = round(2^(S / 12) 10^6) of a shift by S semitones, S first rounded to the six decimals
+    the reference hands to rubberband (``--pitch {S:+.6f}``, workflow.py:129-130); |S| <= 12."""
+    import math
+    s = float(semitones)
+    if not math.isfinite(s) or not abs(round(s, 6)) <= MAX_SEMITONES:
+        raise ValueError(f"pitch shift {semitones!r} outside [-{MAX_SEMITONES:g}, {MAX_SEMITONES:g}] semitones")
+    return int(round(2.0 ** (round(s, 6) / 12.0) * PV_Q))
+
+
+class PvPlan:
+    """``nc_pv_plan`` of files of the given lengths at ratio P / 10^6 (host only): stretched
+    lengths ``ns``, frame counts ``k``, ``frame_base`` [files + 1], the workspace layout
+    ``ws_off`` [6] (mag, V, Phi, frame buffer, empty, scan) and ``ws_bytes``."""
+
+    def __init__(self, P: int, lengths: Sequence[int]):
+        import ctypes as C
+        from . import _native
+        lib = _native.load()
+        n_in = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+        n = len(n_in)
+        self.P, self.n_files = int(P), n
+        self.ns, self.k = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        self.frame_base, self.ws_off = np.zeros(n + 1, np.int64), np.zeros(6, np.int64)
+        nbytes = C.c_size_t(0)
+        _native.check(lib.nc_pv_plan(int(P), n_in.ctypes.data, n, self.ns.ctypes.data, self.k.ctypes.data,
+                                     self.frame_base.ctypes.data, self.ws_off.ctypes.data, C.byref(nbytes)),
+                      "nc_pv_plan")
+        self.ws_bytes = int(nbytes.value)
+        self.total_frames = int(self.frame_base[-1])
+        self.max_frames = int(self.k.max()) if n else 0
+        self.max_ns = int(self.ns.max()) if n else 0
+
+
+def _pv_signals(eng: Engine, src):
+    from .engine import DeviceSignals
+    return src if isinstance(src, DeviceSignals) else eng.upload_signals([np.asarray(a, np.float32) for a in src])
+
+
+def pv_analyze_device(eng: Engine, src, P: int):
+    """Stage 1 alone (``nc_pv_analyze``): (mag [frames, 1025] f32, V [frames, 1025, 2] f32,
+    empty [frames] uint8, PvPlan), all on the device."""
+    sig = _pv_signals(eng, src)
+    plan = PvPlan(P, sig.length)
+    T = max(1, plan.total_frames)
+    up = _Upload()
+    up.add("off", sig.off, np.int64)
+    up.add("len", sig.length, np.int64)
+    up.add("fb", plan.frame_base, np.int64)
+    d = up.commit(eng.dev)
+    mag = torch.empty((T, PV_BINS), dtype=torch.float32, device=eng.dev)
+    v = torch.empty((T, PV_BINS, 2), dtype=torch.float32, device=eng.dev)
+    empty = torch.empty(T, dtype=torch.uint8, device=eng.dev)
+    eng.call("nc_pv_analyze", sig.buf.data_ptr(), d["off"].data_ptr(), d["len"].data_ptr(), d["fb"].data_ptr(),
+             plan.n_files, plan.total_frames, plan.P, mag.data_ptr(), v.data_ptr(), empty.data_ptr(), eng.stream())
+    t = plan.total_frames
+    return mag[:t], v[:t], empty[:t], plan
+
+
+def pv_scan_device(eng: Engine, v: torch.Tensor, empty: torch.Tensor, frame_base: Sequence[int]) -> torch.Tensor:
+    """Stage 2 alone (``nc_pv_scan``): Phi [frames, 1025, 2] f32 from V and the empty flags of
+    files whose frames start at ``frame_base`` [files + 1]."""
+    from . import _native
+    from .engine import h2d
+    fb = np.ascontiguousarray(frame_base, np.int64).reshape(-1)
+    n, total = len(fb) - 1, int(fb[-1])
+    v = v.contiguous()
+    empty = empty.contiguous()
+    if tuple(v.shape) != (total, PV_BINS, 2) or tuple(empty.shape) != (total,):
+        raise ValueError("V / empty do not match frame_base")
+    phi = torch.empty_like(v)
+    if total == 0:
+        return phi
+    ws =eng.workspace("pv_scan", int(_native.load().nc_pv_scan_ws_bytes(total, n)))
+    d = h2d(fb, np.int64, eng.dev)
+    eng.call("nc_pv_scan", v.data_ptr(), empty.data_ptr(), d.data_ptr(), n, total, int(np.diff(fb).max()),
+             phi.data_ptr(), ws.data_ptr(), ws.numel(), eng.stream())
+    return phi
+
+
+def pv_synth_device(eng: Engine, mag: torch.Tensor, phi: torch.Tensor, lengths: Sequence[int], P: int):
+    """Stage 3 alone (``nc_pv_synth``): (DeviceSignals of the stretched signals, device peak[file])
+    from mag / Phi rows laid out by ``PvPlan(P, lengths)``."""
+    from .engine import DeviceSignals
+    plan = PvPlan(P, lengths)
+    mag, phi = mag.contiguous(), phi.contiguous()
+    if tuple(mag.shape) != (plan.total_frames, PV_BINS) or tuple(phi.shape) != (plan.total_frames, PV_BINS, 2):
+        raise ValueError("mag / Phi do not match the plan of these lengths")
+    n = plan.n_files
+    pad = (plan.ns + _ALIGN - 1) // _ALIGN * _ALIGN
+    o_off = np.zeros(n, np.int64)
+    o_off[1:] = np.cumsum(pad)[:-1]
+    up = _Upload()
+    up.add("len", np.asarray(lengths, np.int64), np.int64)
+    up.add("fb", plan.frame_base, np.int64)
+    up.add("out_off", o_off, np.int64)
+    d = up.commit(eng.dev)
+    s = torch.zeros(max(_ALIGN, int(pad.sum())), dtype=torch.float32, device=eng.dev)
+    peak = torch.empty(max(1, n), dtype=torch.float32, device=eng.dev)
+    fbytes = plan.total_frames * PV_N * 4
+    frames = eng.workspace("pv_frames", fbytes)
+    if n:
+        eng.call("nc_pv_synth", mag.data_ptr(), phi.data_ptr(), d["len"].data_ptr(), d["fb"].data_ptr(), n,
+                 plan.total_frames, plan.P, plan.max_ns, frames.data_ptr(), frames.numel(), s.data_ptr(),
+                 d["out_off"].data_ptr(), peak.data_ptr(), eng.stream())
+    return DeviceSignals(s, o_off, plan.ns.copy()), peak[:n]
+
+
+def pv_stretch_device(eng: Engine, src, P: int):
+    """Every file of ``src`` (arrays, or ``DeviceSignals`` already in HBM) stretched in time by
+    P / 10^6 with its pitch kept (the phase vocoder of DESIGN.md §4 "Pitch shift";
+    ``nc_pv_stretch``, six launches), the result left in HBM: (DeviceSignals of the stretched
+    signals, device float32 peak[file] = max |s|, PvPlan).  No host synchronisation."""
+    from .engine import DeviceSignals
+    sig = _pv_signals(eng, src)
+    plan = PvPlan(P, sig.length)
+    n = plan.n_files
+    pad = (plan.ns + _ALIGN - 1) // _ALIGN * _ALIGN
+    o_off = np.zeros(n, np.int64)
+    o_off[1:] = np.cumsum(pad)[:-1]
+    up = _Upload()
+    up.add("off", sig.off, np.int64)
+    up.add("len", sig.length, np.int64)
+    up.add("fb", plan.frame_base, np.int64)
+    up.add("out_off", o_off, np.int64)
+    d = up.commit(eng.dev)
+    s = torch.zeros(max(_ALIGN, int(pad.sum())), dtype=torch.float32, device=eng.dev)
+    peak = torch.empty(max(1, n), dtype=torch.float32, device=eng.dev)
+    if n:
+        ws = eng.workspace("pvoc", plan.ws_bytes)
+        eng.call("nc_pv_stretch", sig.buf.data_ptr(), d["off"].data_ptr(), d["len"].data_ptr(), d["fb"].data_ptr(), n,
+                 plan.total_frames, plan.max_frames, plan.P, plan.max_ns, s.data_ptr(), d["out_off"].data_ptr(),
+                 peak.data_ptr(), ws.data_ptr(), plan.ws_off.ctypes.data, ws.numel(), eng.stream())
+    return DeviceSignals(s, o_off, plan.ns.copy()), peak[:n], plan
+
+
+def pitch_shift_device(eng: Engine, src, semitones: float):
+    """Every file of ``src`` (arrays, or ``DeviceSignals`` already in HBM) shifted in pitch by
+    ``semitones`` with its duration kept: the stretch by P / 10^6 (``pv_stretch_device``), then
+    the speed render at the same ratio (``speed_render_device``), cut to the input's length.
+    Returns (DeviceSignals of length n per file, device float32 peak[file] of the render, P).
+    The peak is that of the whole render, ceil(Ns 10^6 / P) >= n samples.  No host
+    synchronisation."""
+    from .engine import DeviceSignals
+    sig = _pv_signals(eng, src)
+    P = pitch_p(semitones)
+    stretched, _, _ = pv_stretch_device(eng, sig, P)
+    out, peak, _ = speed_render_device(eng, stretched, P / PV_Q)
+    return DeviceSignals(out.buf, out.off, np.asarray(sig.length, np.int64).copy()), peak, P
+
+
+def pitch_shift(eng: Engine, arrays: Sequence[np.ndarray], semitones: float) -> List[np.ndarray]:
+    """Each array shifted by ``semitones`` (float32, the input's length)."""
+    out, _, _ = pitch_shift_device(eng, [np.asarray(a, np.float32) for a in arrays], semitones)
+    hy = out.buf.cpu().numpy()
+    return [hy[o:o + n].copy() for o, n in zip(out.off, out.length)]

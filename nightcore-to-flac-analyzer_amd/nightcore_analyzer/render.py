@@ -12,6 +12,9 @@ include/ncgpu.h): a Kaiser-windowed sinc (beta 10.06, 32 zero crossings a side, 
   (``limit_db``: with the true-peak limiter on the resident render, loudness.py).
 * ``refine_speed`` — render, re-analyse, correct; the render stays in HBM between the two.
 * ``quantize_factor`` / ``hqnc_path`` — the six-decimal factor and the output naming rule.
+* ``pitch_shift`` / ``pitch_file`` / ``refine_pitch`` / ``quantize_semitones`` / ``ps_path`` — the
+  same for the pitch-correction step (``rubberband --pitch S`` in the reference): a phase-vocoder
+  stretch plus the speed render, also parity unpinned (second half of this module).
 """
 from __future__ import annotations
 
@@ -188,4 +191,175 @@ def refine_speed(nightcore, source, *, start: Optional[float] = None, max_render
             break
         if k + 1 < max_renders:
             factor = quantize_factor(factor * residual)
+    return out
+
+
+# ------------------------------------------------------------------ pitch shift (pvoc.hip + speed.hip)
+# What the reference's workflow shells out to `rubberband --pitch S SRC DST` for
+# (workflow.py:121-131) and the pitch-correction loop built on it (workflow.py:652-704).
+# PARITY UNPINNED: rubberband is not installed and the reference holds no pitch shifter; the
+# definition is this project's own (DESIGN.md §4 "Pitch shift", tests/pvoc_ref.py): a plain
+# phase-vocoder time stretch by 2^(S/12) (no transient detection, no phase locking, channels
+# independent) followed by the speed render at the same ratio.
+PITCH_TOLERANCE_ST = 0.5   # |shift| below which the reference renders nothing (workflow.py:640, 697)
+
+
+def quantize_semitones(semitones: float) -> float:
+    """The pitch ratio P / 10^6 really applied for a shift by ``semitones``: S rounded to the
+    six decimals the reference hands to rubberband (``--pitch {S:+.6f}``), P = round(2^(S/12) 10^6)."""
+    from .ops import pitch_p
+    return pitch_p(semitones) / Q
+
+
+def ps_path(src, version: int) -> Path:
+    """``Song PS<version>.wav`` beside ``src`` (workflow._make_ps_path)."""
+    src = Path(src)
+    return src.with_name(f"{src.stem} PS{int(version)}{src.suffix}")
+
+
+def pitch_shift(y: np.ndarray, semitones: float, sr: Optional[int] = None) -> np.ndarray:
+    """The mono signal ``y`` shifted in pitch by ``semitones`` (float32, len(y) samples at the same
+    rate).  ``sr`` is accepted for symmetry with the other seams; the shift does not depend on it."""
+    from .engine import get_engine
+    from . import ops
+    quantize_semitones(semitones)
+    return ops.pitch_shift(get_engine(), [np.asarray(y, np.float32).reshape(-1)], semitones)[0]
+
+
+@dataclass
+class PitchInfo(RenderInfo):
+    """What ``pitch_file`` wrote: a ``RenderInfo`` whose ``factor`` is the pitch ratio P / 10^6
+    and whose ``peak`` is that of the whole render (up to two samples longer than the file) when
+    no limiter ran."""
+    semitones: float = 0.0     # the shift applied (six decimals)
+
+
+def pitch_file(src_path, dst_path, semitones: float, limit_db: Optional[float] = None, *,
+               attack_ms: float = 5.0, release_ms: float = 50.0) -> PitchInfo:
+    """Shift every channel of the WAV file ``src_path`` by ``semitones`` at its own rate and
+    write ``dst_path`` (same rate, channels and length): a 16-bit PCM source gives a 16-bit PCM
+    file (``nc_f32_to_pcm16``), anything else a float32 file.  With a ceiling ``limit_db`` the
+    true-peak limiter runs on the resident result first, as in ``speed_file``."""
+    from .engine import get_engine
+    from .ops import f32_to_pcm16_device, limiter_windows, pitch_shift_device, true_peak_limit_device
+    ratio = quantize_semitones(semitones)
+    if limit_db is not None and not float(limit_db) <= 0.0:
+        raise ValueError(f"limiter ceiling {limit_db!r} dBFS is above full scale")
+    data, sr, fmt = read_wav_channels(src_path)
+    eng = get_engine()
+    out, peak_d, P = pitch_shift_device(eng, list(data), semitones)
+    ch, n_out = data.shape[0], int(data.shape[1])
+    extra = {}
+    if limit_db is not None and ch:
+        wa, wr = limiter_windows(sr, attack_ms, release_ms)
+        out, tp_d, pk_d, lim_d = true_peak_limit_device(eng, out, ch, float(limit_db), wa, wr, in_place=True)
+        peak_d = pk_d
+        extra = dict(true_peak=tp_d, limited_samples=lim_d, limit_db=float(limit_db))
+    if fmt == "pcm16":
+        q, _, clipped_d = f32_to_pcm16_device(eng, out, interleave=True)
+        frames = q[:ch * n_out].cpu().numpy().reshape(n_out, ch).T
+        clipped = int(clipped_d.sum().item())
+        out_fmt = "pcm16"
+    else:
+        hy = out.buf.cpu().numpy()
+        frames = np.stack([hy[o:o + n_out] for o in out.off])
+        clipped = int(np.count_nonzero(np.abs(frames) >= 1.0))
+        out_fmt = "float32"
+    write_wav(dst_path, frames, sr, out_fmt)
+    peak = float(peak_d.max().item()) if ch else 0.0
+    if extra:
+        extra.update(true_peak=float(extra["true_peak"][0].item()),
+                     limited_samples=int(extra["limited_samples"][0].item()))
+    return PitchInfo(Path(dst_path), ratio, n_out, ch, sr, out_fmt, peak, _dbfs(peak), clipped,
+                     semitones=round(float(semitones), 6), **extra)
+
+
+@dataclass
+class PitchRefinement:
+    """The pitch-correction loop's record."""
+    shifts: List[float] = field(default_factory=list)        # every shift rendered (semitones), in order
+    residuals: List[float] = field(default_factory=list)     # nightcore against each render (semitones)
+    converged: bool = False
+    method: str = "chroma_xcorr"                             # of the last estimate
+    initial: Optional[float] = None                          # nightcore against the source (no ``start``)
+    render: Optional[DeviceAudio] = None                     # the last render, resident in HBM
+
+    @property
+    def total_shift(self) -> float:
+        return float(sum(self.shifts))
+
+    @property
+    def corrections(self) -> int:
+        return max(0, len(self.shifts) - 1)
+
+
+def _pitch_shift_estimate(cur, nc, sr: int, log):
+    """(12 log2(median nc_hz / median cur_hz), method) by ``pitch.estimate_pitch_combined``, or
+    (None, method) without voiced values on either side (workflow.py:621-628)."""
+    from . import pitch
+    a_hz, n_hz, method = pitch.estimate_pitch_combined(cur, nc, sr, log=log)
+    va = [v for v in a_hz if v is not None and v > 0]
+    vn = [v for v in n_hz if v is not None and v > 0]
+    if not va or not vn:
+        return None, method
+    return 12.0 * math.log2(float(np.median(vn)) / float(np.median(va))), method
+
+
+def refine_pitch(nightcore, source, *, start: Optional[float] = None, max_renders: int = 4,
+                 log: Optional[Callable[[str], None]] = None) -> PitchRefinement:
+    """The workflow's pitch-correction loop (workflow.py:652-704) without its prompts, on the
+    22 050 Hz mono analysis copies.  First shift: ``start``, else
+    12 log2(median nc_hz / median src_hz) of ``pitch.estimate_pitch_combined``; below 0.5 st
+    nothing is rendered (converged, no shifts).  Each pass shifts the CURRENT render (the source
+    at first) by the shift on the device, re-estimates the nightcore against it and makes the
+    residual the next shift; it stops when the residual is below 0.5 st.  The render stays in
+    HBM between the passes.
+
+    The chroma estimate keeps the reference's ``lag / 3`` (pitch.py: 36 bins per octave folded to
+    12 chroma bins), so without MELODIA a true shift of S semitones is reported as
+    S / 3, and the loop inherits that: it is the reference's loop, not a better one."""
+    from . import pipeline, pitch
+    from .engine import SR, get_engine
+    from .ops import pitch_shift_device
+
+    def _log(msg: str) -> None:
+        if log is not None:
+            log(msg)
+
+    if max_renders < 1:
+        raise ValueError("refine_pitch: max_renders must be at least 1")
+    nc = as_f32(pipeline._load(nightcore, _log, "nightcore"))
+    src = as_f32(pipeline._load(source, _log, "source"))
+    out = PitchRefinement()
+    if start is None:
+        shift, out.method = _pitch_shift_estimate(src, nc, SR, log)
+        out.initial = shift
+        if shift is None:
+            _log("Pitch analysis: insufficient voiced frames — no result.")
+            return out
+    else:
+        shift = float(start)
+    if abs(shift) < PITCH_TOLERANCE_ST:
+        _log(f"Pitch shift {shift:+.6f} st is below the {PITCH_TOLERANCE_ST} st threshold: nothing rendered")
+        out.converged = True
+        return out
+    eng = get_engine()
+    resident = eng.upload_signals([src])
+    host_estimate = pitch.melodia_backend() is not None   # MELODIA reads host arrays
+    for k in range(max_renders):
+        _log(f"Render {k + 1}: pitch {shift:+.6f} st")
+        resident, _, _ = pitch_shift_device(eng, resident, shift)
+        out.render = DeviceAudio(resident.buf[:int(resident.length[0])])
+        out.shifts.append(round(float(shift), 6))
+        cur = out.render.numpy() if host_estimate else out.render
+        residual, out.method = _pitch_shift_estimate(cur, nc, SR, log)
+        if residual is None:
+            _log("  Verification: insufficient voiced frames — cannot confirm correction.")
+            break
+        out.residuals.append(residual)
+        _log(f"  residual ({out.method}): {residual:+.6f} st")
+        if abs(residual) < PITCH_TOLERANCE_ST:
+            out.converged = True
+            break
+        shift = residual
     return out
