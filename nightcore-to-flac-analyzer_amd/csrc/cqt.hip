@@ -327,9 +327,6 @@ __global__ __launch_bounds__(D3_NT) void decimate3_kernel(const float* sig, cons
 // at an atomically reserved position: the median and the histogram that consume them
 // do not depend on the order, so the result stays deterministic.
 constexpr int TP_WAVES = 16;  // 14 -> 16 waves: 537 -> 495 us per 224 chunks (with the LDS Hann window)
-#ifndef TP_DYN_
-#define TP_DYN_ 1  // the workgroup's frames from its LDS counter (0: the static interleave; A/B)
-#endif
 using TpTw = StagedTw<1024>;
 
 struct PeakArgs {
@@ -365,35 +362,17 @@ __global__ __launch_bounds__(TP_WAVES * 64) void tuning_peaks_kernel(PeakArgs a)
   // this lane's Hann taps held across frames (the stft_mel form, round 5): no LDS reads per frame
   float2 hw[16];
   lds_read16_strided<0, 64 * 8>(hw, lds_addr(sh_hann + fft_in_lane(lane0)));
-  const int64_t n_groups = (a.total_tframes + TP_WAVES - 1) / TP_WAVES;
-  const int64_t gb = n_groups * blockIdx.x / gridDim.x, ge = n_groups * (blockIdx.x + 1) / gridDim.x;
-  // The workgroup's work-list frames [f0, f1) go to its waves one at a time (WgFrameQueue, as in
-  // stft_mel); a wave's frames gf rise: their chunk is tracked forward, its bounds and
-  // descriptors reloaded only when gf crosses into a later chunk (no binary search and
-  // dependent loads per frame).  TP_DYN_=0: the static interleave (wave w: frames 16 G + w)
-  const int64_t f0 = gb * TP_WAVES, f1 = std::min<int64_t>(ge * TP_WAVES, a.total_tframes);
-  WgFrameQueue fq(&sh_next, lane0);
-  int c = -1, nt = 0, skip = 0;
-  int64_t cb = 0, ce = -1, coff = 0, clen = 0, ctf = 0;
-  for (int64_t grp = gb; TP_DYN_ || grp < ge; ++grp) {
-    const int64_t gf = TP_DYN_ ? f0 + fq.take(lane0) : grp * TP_WAVES + wave;
-    if (gf >= (TP_DYN_ ? f1 : a.total_tframes)) break;
-    if (gf >= ce) {
-      if (c < 0) {
-        int lo = 0, hi = a.n_chunks - 1;
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (a.tp_base[mid] <= gf) lo = mid;
-          else hi = mid - 1;
-        }
-        c = lo;
-      } else {
-        do ++c;
-        while (c + 1 < a.n_chunks && a.tp_base[c + 1] <= gf);
-      }
-      c = uniform32(c);
-      cb = uniform64(a.tp_base[c]);
-      ce = uniform64(c + 1 < a.n_chunks ? a.tp_base[c + 1] : INT64_MAX);
+  // The workgroup's work-list frames go to its waves one at a time (WgFrameQueue, as in
+  // stft_mel); a wave's frames gf rise: their chunk is tracked forward, its descriptors reloaded
+  // only when gf crosses into a later chunk (SegCursor)
+  WgFrameQueue fq(&sh_next, lane0, a.total_tframes, TP_WAVES);
+  SegCursor cur;
+  int nt = 0, skip = 0;
+  int64_t coff = 0, clen = 0, ctf = 0;
+  for (;;) {
+    const int64_t gf = fq.take(lane0);
+    if (gf >= fq.f1) break;
+    cur.seek<true>(a.tp_base, a.n_chunks, gf, [&](int c) {
       // frames [0, tf_skip[c]) of the chunk were done by the window stage: the work list is
       // the remaining frames only, so the persistent workgroups stay balanced
       skip = uniform32(a.tf_skip ? a.tf_skip[c] : 0);
@@ -401,8 +380,8 @@ __global__ __launch_bounds__(TP_WAVES * 64) void tuning_peaks_kernel(PeakArgs a)
       coff = uniform64(a.chunk_off[c]);
       clen = uniform64(a.chunk_len[c]);
       ctf = uniform64(a.tf_base[c]);
-    }
-    const int t = (int)(gf - cb) + skip;
+    });
+    const int t = (int)(gf - cur.begin) + skip;
     if (t >= nt) continue;
     int lane = lane0;
     asm volatile("" : "+v"(lane));
@@ -462,7 +441,7 @@ __global__ __launch_bounds__(TP_WAVES * 64) void tuning_peaks_kernel(PeakArgs a)
       const int k = kPipLo - 1 + 64 * q + lane;
       if (64 * (q + 1) <= kPipHi - kPipLo + 3 || k <= kPipHi + 1) S[k] = __fsqrt_rn(S[k]);  // test the last round only
     }
-    piptrack_append([&](int k) { return S[k]; }, mx, lane, &a.chunk_npk[c], a.peak_pitch + ctf * kPeakSlots,
+    piptrack_append([&](int k) { return S[k]; }, mx, lane, &a.chunk_npk[cur.s], a.peak_pitch + ctf * kPeakSlots,
                     a.peak_mag + ctf * kPeakSlots, reinterpret_cast<int*>(S + kPipKpk));
   }
 }
@@ -481,24 +460,6 @@ __device__ __forceinline__ int tuning_bin(float r) {
   while (j > 0 && rd < edge(j)) --j;
   while (j < 99 && rd >= edge(j + 1)) ++j;
   return j;
-}
-
-__device__ __forceinline__ unsigned fkey(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float funkey(unsigned k) {
-  return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k);
-}
-
-__device__ __forceinline__ int wave_incl_scan_i(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
 }
 
 // One workgroup per chunk: median of the peak magnitudes (4-pass 8-bit radix select over
@@ -544,48 +505,17 @@ __global__ __launch_bounds__(NT) void tuning_select_kernel(const float* peak_pit
   __shared__ BlockScratch<NT> bs;
   __shared__ int hist[256];
   __shared__ int counts[100];
-  __shared__ int sel[2];
-  const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = blockIdx.x, tid = threadIdx.x;
   const int64_t base = tf_base[c] * kPeakSlots;
   const float* mg = peak_mag + base;
   const float* pt = peak_pitch + base;
   const int N = chunk_npk[c];
   float thr = 0.0f;
   if (N > 0) {
-    int kk = (N - 1) / 2;
-    unsigned prefix = 0, mask = 0;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      for (int i = tid; i < 256; i += NT) hist[i] = 0;
-      __syncthreads();
-      for (int i = tid; i < N; i += NT) {
-        const unsigned key = fkey(mg[i]);
-        if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1);
-      }
-      __syncthreads();
-      if (wave == 0) {
-        const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
-        const int s = h0 + h1 + h2 + h3;
-        const int incl = wave_incl_scan_i(s), excl = incl - s;
-        if (excl <= kk && kk < incl) {
-          int r = kk - excl, d = 4 * lane;
-          const int hh[4] = {h0, h1, h2, h3};
-          for (int q = 0; q < 4; ++q) {
-            if (r < hh[q]) {
-              d = 4 * lane + q;
-              break;
-            }
-            r -= hh[q];
-          }
-          sel[0] = d;
-          sel[1] = r;
-        }
-      }
-      __syncthreads();
-      prefix |= (unsigned)sel[0] << shift;
-      mask |= 255u << shift;
-      kk = sel[1];
-      __syncthreads();
-    }
+    const unsigned prefix = block_kth<NT, unsigned>(N, (N - 1) / 2, [&](int i, unsigned& key) {
+      key = fkey(mg[i]);
+      return true;
+    }, hist, bs);
     const float lo = funkey(prefix);
     if (N & 1) {
       thr = lo;

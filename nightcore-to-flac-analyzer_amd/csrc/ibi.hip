@@ -24,16 +24,6 @@ __global__ __launch_bounds__(256) void ibi_plan_kernel(const int64_t* file_len, 
   block_prefix_table<256>(n_files, frame_base, [&](int f) { return 1 + file_len[f] / hop; });
 }
 
-__device__ __forceinline__ int find_file(const int64_t* base, int n, int64_t g) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (base[mid] <= g) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // ------------------------------------------------------------------------------ A: per-file max
 // (STFT -> mel dB is stft_mel_kernel, stft.hip, in frame_base mode)
 __global__ __launch_bounds__(256) void seq_max_kernel(const float* frame_max, const int64_t* frame_base,
@@ -54,7 +44,7 @@ __global__ __launch_bounds__(256) void ibi_onset_kernel(const float* sdb, const 
   const int lane = threadIdx.x & 63;
   const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (g >= total_frames) return;
-  const int f = find_file(frame_base, n_files, g);
+  const int f = seg_of(frame_base, n_files, g);
   const int64_t t = g - frame_base[f];
   float val = 0.0f;
   if (t >= pad) {
@@ -80,13 +70,7 @@ __global__ void tg_pad_kernel(const float* onset, const int64_t* frame_base, int
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total_padded) return;
   // file of padded index i: xbase(f) = frame_base[f] + f N
-  int lo = 0, hi = n_files - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (frame_base[mid] + (int64_t)mid * N <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  const int f = lo;
+  const int f = seg_of(n_files, i, [&](int m) { return frame_base[m] + (int64_t)m * N; });
   const int64_t base = frame_base[f];
   const int T = (int)(frame_base[f + 1] - base);
   const int u = (int)(i - base - (int64_t)f * N);
@@ -104,7 +88,7 @@ __global__ __launch_bounds__(256) void tg_rinv_kernel(const float* xpad, const i
                                                       const int64_t* b0, const int64_t* b1, double* rinv) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (g >= total_frames) return;
-  const int f = find_file(frame_base, n_files, g);
+  const int f = seg_of(frame_base, n_files, g);
   if (b0) {  // only the frames of this rank's tiles
     const int64_t tb = (g - frame_base[f]) / TG_TB;
     if (tb < b0[f] || tb >= b1[f]) return;
@@ -203,7 +187,7 @@ __global__ __launch_bounds__(256) void ibi_onset_range_kernel(const float* sdb, 
   const int lane = threadIdx.x & 63;
   const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (g >= total_out) return;
-  const int f = find_file(obase, n_files, g);
+  const int f = seg_of(obase, n_files, g);
   const int64_t t = t0[f] + (g - obase[f]);
   float val = 0.0f;
   if (t >= pad) {

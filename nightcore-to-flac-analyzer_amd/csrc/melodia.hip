@@ -56,12 +56,6 @@ struct MelodiaArgs {
   float* pk_sal;              // [total_frames][MD_SALPK]
 };
 
-// monotone float -> uint (larger float -> larger uint), for sort keys
-__device__ __forceinline__ unsigned md_ord(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // ascending bitonic sort of n (a power of two, <= 4 * 1024) keys in LDS by all MD_NT threads
 __device__ void md_bitonic(unsigned long long* key, int n, int tid) {
   for (int size = 2; size <= n; size <<= 1) {
@@ -109,14 +103,7 @@ __global__ __launch_bounds__(MD_NT) void melodia_salience_kernel(MelodiaArgs a) 
   static_assert(4 * MD_ENT * sizeof(int) <= LdsSize<MD_N>::value * sizeof(float2), "entries fit the FFT slot");
 
   for (int64_t g = blockIdx.x; g < a.total_frames; g += gridDim.x) {
-    // file of frame g
-    int lo = 0, hi = a.n_files - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (a.frame_base[mid] <= g) lo = mid;
-      else hi = mid - 1;
-    }
-    const int f = lo;
+    const int f = seg_of(a.frame_base, a.n_files, g);  // file of frame g
     const int64_t t = g - a.frame_base[f], L = a.file_len[f];
     const float* x = a.sig + a.file_off[f];
     const int64_t s0 = t * a.hop - 1024;
@@ -154,7 +141,7 @@ __global__ __launch_bounds__(MD_NT) void melodia_salience_kernel(MelodiaArgs a) 
         const double pos = (double)k + 0.5 * ((double)l - r) / ((double)l - 2.0 * c + r);
         const double val = c - 0.25 * ((double)l - r) * (pos - (double)k);
         const int q = atomicAdd(&ncand, 1);
-        keys[q] = ((unsigned long long)(~md_ord((float)val)) << 32) | (unsigned)k;
+        keys[q] = ((unsigned long long)(~fkey((float)val)) << 32) | (unsigned)k;
       }
     }
     __syncthreads();
@@ -241,7 +228,7 @@ __global__ __launch_bounds__(MD_NT) void melodia_salience_kernel(MelodiaArgs a) 
       const double r = b + 1 < MD_SAL ? sal[b + 1] : -INFINITY;
       if (c > l && c >= r && c > 0.0) {
         const int q = atomicAdd(&npk, 1);
-        keys[q] = ((unsigned long long)(~md_ord((float)c)) << 32) | (unsigned)b;
+        keys[q] = ((unsigned long long)(~fkey((float)c)) << 32) | (unsigned)b;
       }
     }
     __syncthreads();

@@ -1,4 +1,4 @@
-// nc_block.h — workgroup-level primitives (LDS reductions, scans, radix select).
+// nc_block.h — workgroup-level primitives (LDS reductions, scans, radix select, float keys).
 #pragma once
 #include "nc_device.h"
 
@@ -216,6 +216,15 @@ __device__ __forceinline__ void block_argmax(double& v, int& i, BlockScratch<NT>
     }
 }
 
+// Order-preserving keys: a < b as floats <=> key(a) < key(b) as unsigned integers (for radix
+// selects and sort keys; -0 sorts below +0)
+__device__ __forceinline__ unsigned fkey(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float funkey(unsigned k) {
+  return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k);
+}
 __device__ __forceinline__ unsigned long long dkey(double x) {
   unsigned long long u = (unsigned long long)__double_as_longlong(x);
   return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
@@ -225,32 +234,26 @@ __device__ __forceinline__ double dunkey(unsigned long long k) {
   return __longlong_as_double((long long)u);
 }
 
-// k-th smallest (0-based) of vals[i] over i in [0,n) with flag[i] != 0.
-// 8 passes of 8-bit radix select; hist = 256 ints of LDS.
-template <int NT>
-__device__ double block_kth_flagged(const double* vals, const uint8_t* flag, int n, int k, int* hist,
-                                    BlockScratch<NT>& s) {
-  unsigned long long prefix = 0, mask = 0;
-  for (int shift = 56; shift >= 0; shift -= 8) {
+// The k-th smallest (0-based) key among the elements i in [0, n) that take part: key_of(i, key)
+// sets element i's key (unsigned or unsigned long long) and returns whether it does.
+// sizeof(Key) passes of 8-bit radix select, most significant digit first; hist = 256 ints of LDS.
+template <int NT, class Key, class KeyOf>
+__device__ __forceinline__ Key block_kth(int n, int k, KeyOf key_of, int* hist, BlockScratch<NT>& s) {
+  Key prefix = 0, mask = 0;
+  for (int shift = 8 * (int)sizeof(Key) - 8; shift >= 0; shift -= 8) {
     for (int i = threadIdx.x; i < 256; i += NT) hist[i] = 0;
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += NT) {
-      if (!flag[i]) continue;
-      const unsigned long long key = dkey(vals[i]);
-      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1);
+      Key key;
+      if (!key_of(i, key)) continue;
+      if ((key & mask) == prefix) atomicAdd(&hist[(int)(key >> shift) & 255], 1);
     }
     __syncthreads();
     if (threadIdx.x < 64) {  // digit pick: 4 bins per lane + a wave prefix scan (no serial walk)
       const int lane = threadIdx.x;
       const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
       const int sum = h0 + h1 + h2 + h3;
-      int incl = sum;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += y;
-      }
-      const int excl = incl - sum;
+      const int incl = wave_incl_scan(sum), excl = incl - sum;
       if (excl <= k && k < incl) {
         int r = k - excl, d = 4 * lane;
         if (r >= h0) {
@@ -270,13 +273,24 @@ __device__ double block_kth_flagged(const double* vals, const uint8_t* flag, int
       }
     }
     __syncthreads();
-    const unsigned long long d = (unsigned long long)s.l[0];
+    prefix |= (Key)s.l[0] << shift;
+    mask |= (Key)255 << shift;
     k = s.i[0];
-    prefix |= d << shift;
-    mask |= 255ull << shift;
     __syncthreads();
   }
-  return dunkey(prefix);
+  return prefix;
+}
+
+// k-th smallest (0-based) of vals[i] over i in [0,n) with flag[i] != 0.  (Not forced inline: its
+// callers select two or three times each.)
+template <int NT>
+__device__ double block_kth_flagged(const double* vals, const uint8_t* flag, int n, int k, int* hist,
+                                    BlockScratch<NT>& s) {
+  return dunkey(block_kth<NT, unsigned long long>(n, k, [&](int i, unsigned long long& key) {
+    if (!flag[i]) return false;
+    key = dkey(vals[i]);
+    return true;
+  }, hist, s));
 }
 
 }  // namespace nc

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "nc_span.h"
@@ -57,22 +58,31 @@ __device__ __forceinline__ float db10_floor(float x) {
 // idles at the end while another still holds a static share.  A static interleave (wave w: frames
 // 16 G + w) let the waves drift tens of groups apart: stft_mel read 1.62x its algorithmic bytes
 // and ran 9.8 % slower.  Each wave reserves its next frame when it starts one, so the atomic's
-// latency hides under the frame.  `ctr` is zeroed before the workgroup barrier that precedes the
-// first take; frames come out increasing per wave (the descriptor tracking relies on it).
+// latency hides under the frame.  The workgroup's range [f0, f1) is its balanced, contiguous share
+// of `total` frames, counted in groups of `waves`.  `ctr` is a __shared__ int of the kernel that
+// thread 0 zeroes before the workgroup barrier that precedes the construction; frames come out
+// increasing per wave (SegCursor relies on it).
 struct WgFrameQueue {
   int* ctr;
   int nx;  // lane 0: the reserved frame
+  int64_t f0, f1;
   __device__ __forceinline__ int reserve(int lane) {
     int r = 0;
     if (lane == 0) r = atomicAdd(ctr, 1);
     return r;
   }
-  __device__ __forceinline__ WgFrameQueue(int* c, int lane) : ctr(c) { nx = reserve(lane); }
-  // the next frame index of this workgroup's range (>= its frame count: done)
-  __device__ __forceinline__ int take(int lane) {
+  __device__ __forceinline__ WgFrameQueue(int* c, int lane, int64_t total, int waves) : ctr(c) {
+    const int64_t n_groups = (total + waves - 1) / waves;
+    const int64_t gb = n_groups * blockIdx.x / gridDim.x, ge = n_groups * (blockIdx.x + 1) / gridDim.x;
+    f0 = gb * waves;
+    f1 = std::min<int64_t>(ge * waves, total);
+    nx = reserve(lane);
+  }
+  // the workgroup's next global frame (>= f1: done)
+  __device__ __forceinline__ int64_t take(int lane) {
     const int n = __builtin_amdgcn_readfirstlane(nx);
     nx = reserve(lane);
-    return n;
+    return f0 + n;
   }
 };
 
@@ -195,13 +205,6 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned l, unsigned n) {
   return x * q + min(x, r) + l / 8;
 }
 
-// float <-> order-preserving int (for atomicMax on floats of either sign)
-__device__ __forceinline__ int f2ord(float f) {
-  int i = __float_as_int(f);
-  return i >= 0 ? i : i ^ 0x7FFFFFFF;
-}
-__device__ __forceinline__ float ord2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7FFFFFFF); }
-
 // ------------------------------------------------------------------ in-register DFTs
 // exp(-2 pi i m / 16) for the odd m (compile-time after unrolling)
 __device__ __forceinline__ float2 w16(int m) {
@@ -275,6 +278,60 @@ __device__ __forceinline__ int64_t uniform64(int64_t v) {
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
   return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// ------------------------------------------------------------------ segment lookup
+// The last s in [0, n) with key(s) <= g (0 when there is none), key non-decreasing: the segment
+// of element g in a prefix table.  The lo = mid / hi = mid - 1 form picks the last of equal
+// entries, so zero-length segments (a file without frames, a chunk whose tuning frames were all
+// shared) are skipped.
+template <class KeyOf>
+__device__ __forceinline__ int seg_of(int n, int64_t g, KeyOf key) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (key(mid) <= g) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+__device__ __forceinline__ int seg_of(const int64_t* base, int n, int64_t g) {
+  return seg_of(n, g, [&](int m) { return base[m]; });
+}
+
+// A wave's segment while its elements g rise (WgFrameQueue hands them out that way): seek()
+// searches once, afterwards steps forward, and only when g leaves [begin, end); then it calls
+// reload(s) for the kernel's own descriptors of segment s, instead of a binary search and a chain
+// of dependent loads per frame.  s, begin and end are wave-uniform (SGPRs).  OPEN_LAST: the last
+// segment ends at INT64_MAX (base has n entries); otherwise base[n] is read.
+struct SegCursor {
+  int s = -1;
+  int64_t begin = 0, end = -1;
+  template <bool OPEN_LAST, class Reload>
+  __device__ __forceinline__ void seek(const int64_t* base, int n, int64_t g, Reload reload) {
+    if (g < end) return;
+    if (s < 0) {
+      s = seg_of(base, n, g);
+    } else {
+      do ++s;
+      while (s + 1 < n && base[s + 1] <= g);
+    }
+    s = uniform32(s);
+    begin = uniform64(base[s]);
+    end = uniform64(!OPEN_LAST || s + 1 < n ? base[s + 1] : INT64_MAX);
+    reload(s);
+  }
+};
+
+// inclusive prefix sum over the wave's lanes
+__device__ __forceinline__ int wave_incl_scan(int v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(v, o, 64);
+    if (lane >= o) v += y;
+  }
+  return v;
 }
 
 // ------------------------------------------------------------------ Stockham wave FFT

@@ -110,16 +110,6 @@ int pv_plan(int64_t P, const int64_t* n_in, int n_files, int64_t* ns_out, int64_
   return 0;
 }
 
-__device__ __forceinline__ int pv_file_of(const int64_t* base, int n, int64_t g) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (base[mid] <= g) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // every file sample x[i], u - N/2 < i < u + N/2, is +-0 (wave-uniform)
 __device__ __forceinline__ bool pv_span_empty(const float* x, int64_t L, int64_t u, int lane) {
   const int64_t lo = max(u - (PV_N / 2 - 1), (int64_t)0), hi = min(u + (PV_N / 2 - 1), L - 1);
@@ -191,15 +181,12 @@ __global__ __launch_bounds__(PV_THREADS) void pv_analysis_kernel(PvAnaArgs a) {
   fill_staged_tw<1024>(sh_tw, a.tw, threadIdx.x, PV_THREADS);
   __syncthreads();
 
-  const int64_t n_groups = (a.total_frames + PV_WAVES - 1) / PV_WAVES;
-  const int64_t gb = n_groups * blockIdx.x / gridDim.x, ge = n_groups * (blockIdx.x + 1) / gridDim.x;
-  const int64_t f0 = gb * PV_WAVES, f1 = std::min<int64_t>(ge * PV_WAVES, a.total_frames);
   const float2* hann2 = reinterpret_cast<const float2*>(a.hann);
-  WgFrameQueue fq(&sh_next, lane0);
+  WgFrameQueue fq(&sh_next, lane0, a.total_frames, PV_WAVES);
   for (;;) {
-    const int64_t g = f0 + fq.take(lane0);
-    if (g >= f1) break;
-    const int f = uniform32(pv_file_of(a.frame_base, a.n_files, g));
+    const int64_t g = fq.take(lane0);
+    if (g >= fq.f1) break;
+    const int f = uniform32(seg_of(a.frame_base, a.n_files, g));
     const int64_t k = g - uniform64(a.frame_base[f]);
     const int64_t L = uniform64(a.in_len[f]);
     const float* x = a.x + uniform64(a.in_off[f]);
@@ -416,19 +403,16 @@ __global__ __launch_bounds__(PV_THREADS) void pv_synth_kernel(PvSynArgs a) {
   float2* sh_tw = reinterpret_cast<float2*>(smem);
   const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float2* fftbuf = sh_tw + pv_al4(PvTw::size) + wave * LdsSize<1024>::value;
-  __shared__ int sh_next;
+  __shared__ int sh_next;  // the workgroup's frame queue (WgFrameQueue)
   if (threadIdx.x == 0) sh_next = 0;
   fill_staged_tw<1024>(sh_tw, a.tw, threadIdx.x, PV_THREADS);
   __syncthreads();
 
-  const int64_t n_groups = (a.total_frames + PV_WAVES - 1) / PV_WAVES;
-  const int64_t gb = n_groups * blockIdx.x / gridDim.x, ge = n_groups * (blockIdx.x + 1) / gridDim.x;
-  const int64_t f0 = gb * PV_WAVES, f1 = std::min<int64_t>(ge * PV_WAVES, a.total_frames);
   const float2* hann2 = reinterpret_cast<const float2*>(a.hann);
-  WgFrameQueue fq(&sh_next, lane0);
+  WgFrameQueue fq(&sh_next, lane0, a.total_frames, PV_WAVES);
   for (;;) {
-    const int64_t g = f0 + fq.take(lane0);
-    if (g >= f1) break;
+    const int64_t g = fq.take(lane0);
+    if (g >= fq.f1) break;
     int lane = lane0;
     asm volatile("" : "+v"(lane));
     const float* mrow = a.mag + g * PV_BINS;

@@ -56,16 +56,6 @@ struct SpecArgs {
   unsigned long long* span = nullptr;  // nc_profile execution span (nc_device.h)
 };
 
-__device__ __forceinline__ int sf_file_of(const int64_t* base, int n, int64_t g) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (base[mid] <= g) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 __host__ __device__ __forceinline__ int sf_al4(int n) { return (n + 3) & ~3; }
 
 static size_t spectral_frames_lds_bytes() {
@@ -84,30 +74,17 @@ __global__ __launch_bounds__(SF_THREADS) void spectral_frames_kernel(SpecArgs a)
   fill_staged_tw<1024>(sh_tw, a.tw, threadIdx.x, SF_THREADS);
   __syncthreads();
 
-  const int64_t n_groups = (a.total_frames + SF_WAVES - 1) / SF_WAVES;
-  const int64_t gb = n_groups * blockIdx.x / gridDim.x, ge = n_groups * (blockIdx.x + 1) / gridDim.x;
-  // The workgroup's frames [f0, f1) go to its waves one at a time (WgFrameQueue, the stft_mel
-  // scheme); a wave's frames rise: the file and its descriptors (bounds, length, offset, band
-  // bins) are reloaded only when g crosses into a later file, instead of a binary search and a
-  // chain of dependent loads per frame
-  const int64_t f0 = gb * SF_WAVES, f1 = std::min<int64_t>(ge * SF_WAVES, a.total_frames);
-  WgFrameQueue fq(&sh_next, lane0);
-  int f = -1;
-  int64_t fb = 0, fe = -1, L = 0, off = 0;
+  // The workgroup's frames go to its waves one at a time (WgFrameQueue, the stft_mel scheme); a
+  // wave's frames rise: the file and its descriptors (length, offset, band bins) are reloaded
+  // only when g crosses into a later file (SegCursor)
+  WgFrameQueue fq(&sh_next, lane0, a.total_frames, SF_WAVES);
+  SegCursor cur;
+  int64_t L = 0, off = 0;
   int blo[SF_NBANDS], bhi[SF_NBANDS];
   for (;;) {
-    const int64_t g = f0 + fq.take(lane0);
-    if (g >= f1) break;
-    if (g >= fe) {
-      if (f < 0) {
-        f = sf_file_of(a.frame_base, a.n_files, g);
-      } else {
-        do ++f;
-        while (f + 1 < a.n_files && a.frame_base[f + 1] <= g);
-      }
-      f = uniform32(f);
-      fb = uniform64(a.frame_base[f]);
-      fe = uniform64(a.frame_base[f + 1]);
+    const int64_t g = fq.take(lane0);
+    if (g >= fq.f1) break;
+    cur.seek<false>(a.frame_base, a.n_files, g, [&](int f) {
       L = uniform64(a.file_len[f]);
       off = uniform64(a.file_off[f]);
       const int* bb = a.band_bins + f * 2 * SF_NBANDS;
@@ -116,8 +93,8 @@ __global__ __launch_bounds__(SF_THREADS) void spectral_frames_kernel(SpecArgs a)
         blo[b] = uniform32(bb[2 * b]);
         bhi[b] = uniform32(bb[2 * b + 1]);
       }
-    }
-    const int64_t t = g - fb;
+    });
+    const int64_t t = g - cur.begin;
     const float* x = a.sig + off;
     const int64_t s0 = t * 512 - 1024;
 
@@ -237,7 +214,7 @@ __global__ __launch_bounds__(SF_THREADS) void spectral_frames_kernel(SpecArgs a)
     fs = dpp_add_f64<0xB1>(fs);   // quad_perm [1,0,3,2]
     fs = dpp_add_f64<0x4E>(fs);   // quad_perm [2,3,0,1]
     fs = dpp_add_f64<0x141>(fs);  // row_half_mirror: the other quad of the 8 lanes
-    const double hz = a.bin_hz[f];
+    const double hz = a.bin_hz[cur.s];
     double* r = a.rec + g * SF_REC;
     auto lane_f64 = [&](int l) {
       const long long b = __double_as_longlong(fs);
@@ -256,55 +233,14 @@ __global__ __launch_bounds__(SF_THREADS) void spectral_frames_kernel(SpecArgs a)
   }
 }
 
-// k-th smallest (0-based) of n non-negative floats: 4 passes of 8-bit radix select on the
-// IEEE bits (monotonic for x >= 0); hist = 256 ints of LDS.
+// k-th smallest (0-based) of n floats (block_kth on their order-preserving keys); hist = 256
+// ints of LDS.
 template <int NT>
-__device__ float sf_kth(const float* x, int n, int k, int* hist, BlockScratch<NT>& s) {
-  unsigned prefix = 0, mask = 0;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    for (int i = threadIdx.x; i < 256; i += NT) hist[i] = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += NT) {
-      const unsigned key = __float_as_uint(x[i]);
-      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1);
-    }
-    __syncthreads();
-    if (threadIdx.x < 64) {  // digit pick: 4 bins per lane + a wave prefix scan
-      const int lane = threadIdx.x;
-      const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
-      const int sum = h0 + h1 + h2 + h3;
-      int incl = sum;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += y;
-      }
-      const int excl = incl - sum;
-      if (excl <= k && k < incl) {
-        int r = k - excl, d = 4 * lane;
-        if (r >= h0) {
-          r -= h0;
-          ++d;
-          if (r >= h1) {
-            r -= h1;
-            ++d;
-            if (r >= h2) {
-              r -= h2;
-              ++d;
-            }
-          }
-        }
-        s.i[0] = d;
-        s.i[1] = r;
-      }
-    }
-    __syncthreads();
-    prefix |= (unsigned)s.i[0] << shift;
-    mask |= 255u << shift;
-    k = s.i[1];
-    __syncthreads();
-  }
-  return __uint_as_float(prefix);
+__device__ __forceinline__ float sf_kth(const float* x, int n, int k, int* hist, BlockScratch<NT>& s) {
+  return funkey(block_kth<NT, unsigned>(n, k, [&](int i, unsigned& key) {
+    key = fkey(x[i]);
+    return true;
+  }, hist, s));
 }
 
 // One workgroup per file.  stats[f][0..7] = {sum centroid, sum rolloff Hz, 5 band |S| sums,

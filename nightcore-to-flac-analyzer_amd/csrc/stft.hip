@@ -46,22 +46,17 @@ constexpr size_t SM_LDS_RESERVE = 150 * 1024;
 #endif
 // Round 6 (profiles/r6_stft_sync_*.txt): with a static interleave (wave w: frames
 // 16 G + w) the free-running waves of a workgroup drift apart by tens of frame groups, so the 4x
-// frame overlap is re-fetched from beyond the L2: reads 1.62x the algorithmic bytes.  Keeping them together with a bare s_barrier every 8 groups
-// (SM_SYNC_=8) cuts the reads to 1.02x, but costs 3.6 % of the kernel's time (457.4 against 441.3 us
-// per 560 windows; every 32 groups: 1.44x, +1.2 %; __syncthreads every 1-32 groups: +4-22 %); each
-// wave walking its own contiguous run (a probe since removed) reads 1.96x and is 1-10 % slower.  The kernel is
-// not bound by its HBM bytes, so the waves stay free-running.
-#ifndef SM_SYNC_
-#define SM_SYNC_ 0  // probe (static interleave only): a barrier every SM_SYNC_ frame groups
-#endif
+// frame overlap is re-fetched from beyond the L2: reads 1.62x the algorithmic bytes.  Keeping them
+// together with a bare s_barrier every 8 groups (a probe since removed) cut the reads to 1.02x, but
+// cost 3.6 % of the kernel's time (457.4 against 441.3 us per 560 windows; every 32 groups: 1.44x,
+// +1.2 %; __syncthreads every 1-32 groups: +4-22 %); each wave walking its own contiguous run
+// (a probe since removed) read 1.96x and was 1-10 % slower.  The kernel is not bound by its HBM
+// bytes, so the waves stay free-running.
 // The fix (round 6): the sixteen waves take the workgroup's frames one at a time from an LDS
-// counter (SM_DYN_, default), so the frames in flight are always the sixteen most recently taken,
+// counter (WgFrameQueue), so the frames in flight are always the sixteen most recently taken,
 // whatever the waves' relative speeds: reads 1.62x -> 1.00x algorithmic, 443.1 -> 399.8 us per 560
 // windows (-9.8 %), the wave that finishes first no longer idles at the end of the range, outputs
-// bit-identical (profiles/r6_stft_dyn_var_bench.txt).  SM_DYN_=0 restores the static interleave.
-#ifndef SM_DYN_
-#define SM_DYN_ 1
-#endif
+// bit-identical (profiles/r6_stft_dyn_var_bench.txt).  The static interleave was removed with it.
 using SmTw = StagedTw<1024>;  // per-stage twiddle table in LDS (conflict-free reads)
 
 // Mel band loops with compile-time trip counts, unrolled in load batches: 562-576 against
@@ -93,16 +88,6 @@ __device__ __forceinline__ void mel_unrolled(const float* pw, const float4* w4, 
     for (int j = 0; j < kMelB; ++j)
       if (j0 + j < J) acc = fmaf(w[j].w, p[j].w, fmaf(w[j].z, p[j].z, fmaf(w[j].y, p[j].y, fmaf(w[j].x, p[j].x, acc))));
   }
-}
-
-__device__ __forceinline__ int seq_of_frame(const int64_t* base, int n, int64_t g) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (base[mid] <= g) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
 }
 
 __host__ __device__ __forceinline__ int al4(int n) { return (n + 3) & ~3; }
@@ -249,7 +234,7 @@ __global__ __launch_bounds__(SM_THREADS) void stft_mel_kernel(StftMelArgs a) {
   int* sh_mt = reinterpret_cast<int*>(sh_hann + SM_HANN2);
   float2* slot = reinterpret_cast<float2*>(sh_mt + SM_MT) + wave * SM_HALF;
 
-  __shared__ int sh_next;  // SM_DYN_: the workgroup's next frame
+  __shared__ int sh_next;  // the workgroup's frame queue (WgFrameQueue)
   if (threadIdx.x == 0) sh_next = 0;
   fill_staged_tw<1024>(sh_tw, a.tw, threadIdx.x, SM_THREADS);
   for (int i = threadIdx.x; i < SM_HANN2; i += SM_THREADS) sh_hann[i] = reinterpret_cast<const float2*>(a.hann2048)[i];
@@ -264,13 +249,14 @@ __global__ __launch_bounds__(SM_THREADS) void stft_mel_kernel(StftMelArgs a) {
   for (int i = threadIdx.x & 63; i < SM_HALF; i += 64) slot[i] = make_float2(0.f, 0.f);
   __syncthreads();
 
-  const int64_t n_groups = (a.total_frames + SM_WAVES - 1) / SM_WAVES;
-  const int64_t gb = n_groups * blockIdx.x / gridDim.x, ge = n_groups * (blockIdx.x + 1) / gridDim.x;
+  WgFrameQueue fq(&sh_next, lane0, a.total_frames, SM_WAVES);
   float2 hw[16];  // this lane's Hann taps, w[2 (j1 + 64 r)] and w[2 (j1 + 64 r) + 1]
   lds_read16_strided<0, 64 * 8>(hw, lds_addr(sh_hann + sm_j1(lane0)));
-  // the wave's frames g = grp * SM_WAVES + wave rise by SM_WAVES: their sequence is tracked
-  // forward, its bounds, flags, length and offset reloaded only when g crosses into a later
-  // sequence, instead of a 64-bit division or binary search and dependent loads per frame.
+  // the wave's frames g rise: their sequence is tracked forward, its bounds, flags, length and
+  // offset reloaded only when g crosses into a later sequence, instead of a 64-bit division or
+  // binary search and dependent loads per frame.  (SegCursor's scheme spelled out: the
+  // equal-length mode has no table, and through the cursor the edge path's address arithmetic
+  // compiles differently.)
   // (The workgroups keep static, balanced frame ranges: a chip-wide counter handing each wave runs
   // of N contiguous frames measured 4.64 (N = 128) and 11.5 (N = 512) against 3.42 ms per step
   // isolated — runs leave waves idle and break the CU's shared frame overlap,
@@ -279,23 +265,12 @@ __global__ __launch_bounds__(SM_THREADS) void stft_mel_kernel(StftMelArgs a) {
   int64_t sb = 0, se = -1, t0 = 0, L = 0, off = 0;
   int wc = -1;
   bool act = true;
-  // SM_DYN_: the workgroup's frames [f0, f1) one at a time from its LDS counter (WgFrameQueue)
-  const int64_t f0 = gb * SM_WAVES, f1 = std::min<int64_t>(ge * SM_WAVES, a.total_frames);
-  WgFrameQueue fq(&sh_next, lane0);
-  for (int64_t grp = gb; SM_DYN_ || grp < ge; ++grp) {
-    int64_t g;
-    if (SM_DYN_) {
-      g = f0 + fq.take(lane0);
-      if (g >= f1) break;
-    } else {
-      // (the probe's barrier orders nothing in memory: a bare s_barrier, no vmcnt / lgkmcnt drain)
-      if (SM_SYNC_ > 0 && (grp - gb) % (SM_SYNC_ > 0 ? SM_SYNC_ : 1) == 0) __builtin_amdgcn_s_barrier();
-      g = grp * SM_WAVES + wave;
-      if (g >= a.total_frames) break;
-    }
+  for (;;) {
+    const int64_t g = fq.take(lane0);
+    if (g >= fq.f1) break;
     if (g >= se) {
       if (s < 0) {
-        s = a.frame_base ? seq_of_frame(a.frame_base, a.n_seq, g) : (int)(g / a.uniform_T);
+        s = a.frame_base ? seg_of(a.frame_base, a.n_seq, g) : (int)(g / a.uniform_T);
       } else if (a.frame_base) {
         do ++s;
         while (s + 1 < a.n_seq && a.frame_base[s + 1] <= g);

@@ -190,6 +190,35 @@ def test_chroma_silent_chunk_is_zero(gpu_ctx):
     assert np.all(got == 0.0)
 
 
+@pytest.mark.parametrize("case", ["few", "deep"])
+def test_chroma_short_chunks_between_long_ones_equal_alone(case):
+    """Chunks of 5 to 9 tuning frames between long ones, so a tuning_peaks wave whose chunk was a
+    long one finds its next frame several chunks ahead (the chunk cursor advances more than one
+    step): tuning and chroma of every checked chunk are those of the chunk alone, bit for bit.
+    "few": long, short, short, short, long.  "deep": seven 20 s chunks either side of six short
+    ones, 12 000 tuning frames in all, so that on a chip of up to 256 CUs a workgroup owns more
+    frames than it has waves and meets the short chunks with every wave past its first lookup."""
+    from nightcore_analyzer import engine as E, ops
+    eng = E.get_engine(0)
+    nc, src = synth.make_pair(30.0, 1003)
+    sig = np.concatenate([src, nc]).astype(np.float32)
+    if case == "few":
+        spans = [(1, 2048 * 40 + 1), (3, 2048), (len(src) + 5, 3000), (7, 4096), (len(src) + 2, 2048 * 41 - 1)]
+        check = range(len(spans))
+    else:
+        longs = [(1000 * i + (i & 1), 441000) for i in range(14)]
+        shorts = [(3, 2048), (len(src) + 5, 2048), (7, 3000), (11, 2048), (len(src) + 2, 2500), (13, 4096)]
+        spans = longs[:7] + shorts + longs[7:]
+        check = range(6, 14)
+    chunks = [sig[o:o + n] for o, n in spans]
+    got, tun, _ = ops.chroma_means(eng, chunks)
+    assert np.isfinite(got).all() and np.isfinite(tun).all()
+    for i in check:
+        one, t1, _ = ops.chroma_means(eng, [chunks[i]])
+        assert tun[i] == t1[0], (i, spans[i])
+        assert np.array_equal(got[i], one[0]), (i, spans[i])
+
+
 def test_chroma_ragged_chunks_across_decimator_tiles(gpu_ctx):
     """The fused octave chain (cqt.hip decimate3_kernel) owns 2048 level-0 samples per tile:
     chunk lengths one sample either side of a tile edge and at odd offsets (no aligned

@@ -83,6 +83,28 @@ def test_spectral_batch_mixed_rates_equals_single(eng):
         assert b == spectral.analyze_arrays(y, sr)
 
 
+@pytest.mark.parametrize("long_lens", [(2 * 22050, 2 * 22050), (6167 * 512, 6119 * 512)])
+def test_spectral_batch_short_files_between_long_ones_equals_single(eng, long_lens):
+    """A long file, then five files of 1 to 5 frames (1, 511, 512, 600 and 2 048 samples), so a
+    wave's next frame lies several files ahead and its file cursor advances more than one step,
+    then another long file; one rate.  Two 2 s files; or 6 168 and 6 120 frames, 12 299 in all, so
+    that on a chip of up to 256 CUs a workgroup's share (48 frames) exceeds its 16 waves, and the
+    short files start 24 frames into the share of the workgroup that meets them: each of its
+    waves has a file already."""
+    sr = 22050
+    rng = np.random.default_rng(77)
+    lens = (long_lens[0], 1, 511, 512, 600, 2048, long_lens[1])
+    sigs = []
+    for i, n in enumerate(lens):
+        t = np.arange(n, dtype=np.float64) / sr
+        y = 0.3 * np.sin(2 * np.pi * (220.0 * (i + 1)) * t) + 0.05 * rng.standard_normal(n)
+        sigs.append((y.astype(np.float32), sr))
+    batch = eng.spectral(sigs)
+    assert len(batch) == len(sigs)
+    for i, (s, b) in enumerate(zip(sigs, batch)):
+        assert b == eng.spectral([s])[0], i
+
+
 _NUM = __import__("re").compile(r"[-+]?\d+(?:\.\d+)?")
 
 

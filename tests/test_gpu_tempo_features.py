@@ -299,6 +299,45 @@ def test_ibi_onset_ragged_batch(gpu_ctx, hop):
         assert np.array_equal(fb1, [0, len(ref)]) and np.array_equal(alone[0], ons[i]), i
 
 
+@pytest.mark.parametrize("hop", [64, 512])
+def test_ibi_onset_short_files_between_long_ones(gpu_ctx, hop):
+    """A 41-frame file first, so every wave of the STFT workgroup has looked its file up once; then
+    six files of 1 to 4 frames, so a wave's next frame lies several files ahead and its segment
+    cursor advances more than one step (with the tiny files first, as in the ragged batch above,
+    every first lookup is the search); a second long file ends the batch."""
+    lens = (40 * hop, 0, 1, hop, hop + 1, 0, 3 * hop, 40 * hop)
+    scale = [1.0, 30.0, 1e-3, 1.0, 30.0, 1e-3, 1.0, 30.0]
+    files = [C.scaled(C.music(n, start=1000 * i), s) for i, (n, s) in enumerate(zip(lens, scale))]
+    ons, fb = run_ibi_onset(gpu_ctx, files, hop)
+    assert np.array_equal(fb, np.concatenate([[0], np.cumsum([1 + n // hop for n in lens])]))
+    for i, y in enumerate(files):
+        ref = ncref.onset_strength(y, SR, hop)
+        yard = C.onset_yardstick(ref, C.mel_db_f32(y, SR, hop), hop)
+        d, tol = float(np.max(np.abs(ons[i] - ref))), C.tol_f32(yard, np.max(ref))
+        print(f"[c] hop {hop} file {i} len {len(y)}: onset {d:.2e} (yardstick {yard:.2e}, tol {tol:.2e})")
+        assert ons[i].shape == ref.shape and np.isfinite(ons[i]).all()
+        assert d <= tol, (i, d, tol)
+        alone, fb1 = run_ibi_onset(gpu_ctx, [y], hop, lead=0)
+        assert np.array_equal(fb1, [0, len(ref)]) and np.array_equal(alone[0], ons[i]), i
+
+
+def test_ibi_onset_short_files_deep_in_a_workgroup_range(gpu_ctx):
+    """The same six short files between two of ~6 100 frames (hop 64): 12 299 frames, so that on a
+    chip of up to 256 CUs a workgroup's share (48 frames) exceeds its 16 waves, and the short
+    files start 24 frames into the share of the workgroup that meets them: each of its waves has
+    a file already and steps its cursor up to seven files forward.  Batch = alone, bit for bit
+    (the oracle comparison of such files is test_ibi_onset_ragged_batch's)."""
+    hop = 64
+    lens = (6167 * hop, 0, 1, hop, hop + 1, 0, 3 * hop, 6119 * hop)
+    starts = (0, 1000, 2000, 3000, 4000, 5000, 6000, 400000)
+    files = [C.music(n, start=s) for n, s in zip(lens, starts)]
+    ons, fb = run_ibi_onset(gpu_ctx, files, hop)
+    assert np.array_equal(fb, np.concatenate([[0], np.cumsum([1 + n // hop for n in lens])]))
+    for i, y in enumerate(files):
+        alone, _ = run_ibi_onset(gpu_ctx, [y], hop, lead=0)
+        assert np.isfinite(ons[i]).all() and np.array_equal(alone[0], ons[i]), i
+
+
 # --------------------------------------------------------------------------- d. nc_ibi_tempogram
 @lru_cache(maxsize=None)
 def _env_ref(kind, T, N):
