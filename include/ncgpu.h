@@ -181,6 +181,55 @@ int nc_chroma_mean(nc_ctx* ctx, const float* sig, const int64_t* chunk_off, cons
                    float* out_tuning, int* out_tuning_idx, int* out_tuning_margin, void* ws, size_t ws_bytes,
                    void* stream);
 
+/* Where nc_chroma_mean leaves its intermediates in the caller's workspace (host only,
+ * launches nothing; for inspection and tests, no reference equivalent).  The launcher
+ * carves its workspace through the same function, so the answer cannot drift from it.
+ * Fills out[0 .. 26) (cap >= 26) and returns 26, or -2 on a bad argument:
+ *   [0]  entries written (26)
+ *   byte offsets into ws, each section 256-byte aligned (n = n_chunks):
+ *   [1]  oct_off    int64[n][7]  float offset of level o of chunk c inside ws_oct
+ *                   (o = 0: -1, level 0 is the chunk itself inside sig)
+ *   [2]  oct_len    int64[n][7]  length of level o: L_0 = chunk_len, L_{o+1} = ceil(L_o / 2)
+ *   [3]  n_frames   int32[n]     CQT frames T = min over o of 1 + L_o / (512 >> o)
+ *   [4]  n_tframes  int32[n]     tuning STFT frames 1 + chunk_len / 512
+ *   [5]  chunk_npk  int32[n]     piptrack peaks in the chunk's list (nc_chroma_mean_shared
+ *                                counts into the caller's array instead)
+ *   [6]  tuning_idx int32[n]     used only when out_tuning_idx is NULL
+ *   [7]  tf_base    int64[n+1]   prefix sum of n_tframes
+ *   [8]  oct_base   int64[n+1]   prefix sum of the chunks' octave-buffer floats
+ *   [9]  ws_oct     float[]      decimated levels 1..6, y_{o+1} = sqrt(2) halfband(y_o)[::2];
+ *                                each level padded to a multiple of 64 floats (the padding
+ *                                is not written)
+ *   [10] peak_pitch float[]      chunk c's peaks at [tf_base[c] * kPeakSlots ..
+ *   [11] peak_mag   float[]      + chunk_npk[c]), in no particular order (appended at an
+ *                                atomic position); peak_mag is 2x piptrack's magnitude.
+ *                                nc_chroma_mean_shared uses the caller's lists instead
+ *   [12] partial    double[]     per-tile sums of the normalised chroma (cqt_tail)
+ *   [13] tp_base    int64[n+1]   prefix of the tuning frames the chain itself computes
+ *   [14] xmax       float[]      max |level 0| per decimation tile of chunk c, at slot
+ *                                c + oct_off[c][3] / 256 + tile
+ *   [15] gpart      float[][7][12]  row tf_base[c] + t (t < n_frames[c]) holds frame t's
+ *                                chroma partial sums per octave: gpart[row][k][j] is the sum
+ *                                of |C| over CQT bins 36 k + {3j - 1, 3j, 3j + 1} (3j - 1
+ *                                wraps to 36 k + 35 for j = 0), k = 0 the lowest octave
+ *                                (bins 0..35, from level 6) .. k = 6 the highest (bins
+ *                                216..251, from level 0, the chunk itself); column j is
+ *                                chroma j (0 = C, 1 = C#, .. 11 = B).  The device's octave
+ *                                index o (levels, oct_ex) is 6 - k
+ *   [16] oct_ex     int32[n][7]  f16 split exponent of level o: the CQT scales the level's
+ *                                samples by 2^oct_ex, 0 for a silent chunk
+ *   [17] bytes carved (nc_chroma_workspace_bytes is this plus slack)
+ *   constants: [18] D3_TILE level-(base + 3) outputs per decimation workgroup (8 D3_TILE
+ *   level-0 samples for levels 1-3, 64 D3_TILE for levels 4-6), [19] kPeakSlots peak slots
+ *   per tuning frame, [20] CH_FR frames per tile of the CQT of levels 3-6, [21] C2_FR and
+ *   [22] C2_NW frames per tile and tiles per workgroup of the CQT of levels 0-2, [23] CM_FR
+ *   frames per tail tile, [24] kHalfbandK (the decimator has 2 kHalfbandK + 1 taps).
+ *   [25] head       float[n][4], then int64[n]: the first four samples of every chunk (zeros
+ *                   past its end) and where the CQT of level 0 reads each chunk, in floats from
+ *                   sig: chunk_off[c], or for a chunk under 4 samples the distance of its head
+ *                   slot from sig, so that no 16-byte load passes the end of the caller's buffer */
+int nc_chroma_workspace_layout(const nc_ctx* ctx, int n_chunks, int64_t total_len, int64_t* out, int cap);
+
 /* ---------------------------------------------------------------------------
  * K9-K11 with shared tuning frames (optional fusion; same results as the pair
  * nc_window_stage + nc_chroma_mean).  The first tp_frames tuning frames (2048 / 512,

@@ -57,7 +57,14 @@ __device__ __forceinline__ int64_t chunk_oct_floats(int64_t L) {
 __global__ __launch_bounds__(256) void chroma_plan_kernel(const int64_t* chunk_len, int n, int64_t* oct_off,
                                                            int64_t* oct_len, int* n_frames, int* n_tframes,
                                                            int64_t* tf_base, int64_t* oct_base,
-                                                           const int* tf_skip, int64_t* tp_base) {
+                                                           const int* tf_skip, int64_t* tp_base, const float* sig,
+                                                           const int64_t* chunk_off, float* head, int64_t* cq_off) {
+  // cqt_mfma_low's edge tiles load whole 16-byte pieces, which a chunk of 1-3 samples does not
+  // hold: head[c][0..4) = such a chunk's samples, then zeros, and cq_off[c] = where octave 0
+  // reads chunk c, in floats from sig: chunk_off[c], or the head slot's distance from sig (both
+  // are float arrays in the one flat address space, so sig + cq_off[c] is the slot exactly)
+  for (int i = threadIdx.x; i < 4 * n; i += 256) head[i] = (i & 3) < chunk_len[i >> 2] ? sig[chunk_off[i >> 2] + (i & 3)] : 0.0f;
+  for (int c = threadIdx.x; c < n; c += 256) cq_off[c] = chunk_len[c] < 4 ? (int64_t)((head + 4 * c) - sig) : chunk_off[c];
   block_prefix_table<256>(n, oct_base, [&](int c) { return chunk_oct_floats(chunk_len[c]); });
   block_prefix_table<256>(n, tf_base, [&](int c) { return 1 + chunk_len[c] / 512; });
   // tuning frames the tuning kernel itself computes (all but the skipped leading ones)
@@ -451,12 +458,21 @@ __global__ __launch_bounds__(TP_WAVES * 64) void tuning_peaks_kernel(PeakArgs a)
 // latency-bound loops over the peak list; wave-aggregated top-byte counts, which remove
 // the LDS same-address conflicts, measured no better)
 constexpr int TS_NT = 1024;
+// numpy's linspace(-0.5, 0.5, 101)[i] (i < 100): the product and the sum are rounded separately.
+// Contracted into one fma (the device default) entry 50 is 1.04e-17 instead of 0: a chunk
+// without peaks reported that tuning instead of 0.0, and a residual of exactly 0 (a pitch of
+// 27.5 * 2^k Hz) fell into bin 49
+__device__ __forceinline__ double tuning_edge(int i) {
+#pragma clang fp contract(off)
+  const double p = (double)i * (1.0 / 100.0);
+  return p + (-0.5);
+}
 __device__ __forceinline__ int tuning_bin(float r) {
   // np.histogram(residual, linspace(-0.5, 0.5, 101)) bin of r (exact edge comparisons in f64)
   const double rd = (double)r;
   int j = (int)floor((rd + 0.5) * 100.0);
   j = max(0, min(99, j));
-  auto edge = [](int i) { return i == 100 ? 0.5 : (double)i * (1.0 / 100.0) + (-0.5); };
+  auto edge = [](int i) { return i == 100 ? 0.5 : tuning_edge(i); };
   while (j > 0 && rd < edge(j)) --j;
   while (j < 99 && rd >= edge(j + 1)) ++j;
   return j;
@@ -557,7 +573,7 @@ __global__ __launch_bounds__(NT) void tuning_select_kernel(const float* peak_pit
         if (counts[j] > counts[best]) best = j;
     }
     tuning_idx[c] = best;
-    tuning_val[c] = (float)((double)best * (1.0 / 100.0) + (-0.5));
+    tuning_val[c] = (float)tuning_edge(best);  // index 50 (and no peak at all): 0.0
     if (tuning_margin) {  // decision margin: argmax count minus the runner-up's (0 = tie, first index won)
       int second = -1;
       for (int j = 0; j < 100; ++j)
@@ -666,7 +682,7 @@ size_t cqm_lds_bytes() { return CM_KBYTES > CM_MBYTES ? CM_KBYTES : CM_MBYTES; }
 
 struct CqmArgs {
   const float* sig;
-  const int64_t* chunk_off;
+  const int64_t* chunk_off;  // the plan's copy: a chunk under 4 samples points at its head slot
   const int64_t* oct_off;
   const int64_t* oct_len;
   const int* n_frames;
@@ -1078,6 +1094,11 @@ __device__ __forceinline__ void c2_wait_slice(bool last) {
 // Block g of this wave's tile into registers: 8-sample unit u = 64 k + lane is row min(u / 4,
 // NR - 1), piece u % 4, samples s0 + R H + 32 g + 8 p + [0, 8).  Edge tiles load from clamped
 // positions (every load stays inside the signal); c2_split puts the true samples in place.
+// A chunk under 4 samples holds no whole piece inside the caller's buffer (the clamped piece
+// would reach up to 12 bytes past it): the plan points octave 0 of such a chunk at its head
+// slot in the workspace (chroma_plan_kernel: its samples, then zeros), so this kernel issues
+// the same loads and c2_pick finds the same samples at the same offsets.  Levels 1-2 of such a
+// chunk sit in 64-float slots of the workspace already.
 template <int OCT>
 __device__ __forceinline__ void c2_stage(cm_u4 (&st)[C2_NL], const float* y, int64_t s0, int g, int64_t Ly,
                                          bool edge, int lane) {
@@ -1446,25 +1467,80 @@ struct ChromaWs {
   float* xmax;  // decimate3 workgroup maxima of |level 0|
   float* gpart; // [tuning frame][7][12] octave chroma partial rows (hybrid CQT)
   int* oct_ex;  // [n][7] f16 split exponents of the CQT operands
+  float* head;  // [n][4] first samples of every chunk
+  int64_t* cq_off;  // [n] after head: where the low-octave CQT reads each chunk (chroma_plan_kernel)
 };
 
 static inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
 
-size_t chroma_ws_bytes(int n, int64_t total_len) {
+// The one carving of the workspace: sections in this order, each 256-byte aligned.  The launcher
+// takes its pointers from it, chroma_ws_bytes its size, and nc_chroma_workspace_layout
+// (include/ncgpu.h, which documents every section) reports the same offsets.
+enum ChromaSec {
+  CS_OCT_OFF, CS_OCT_LEN, CS_N_FRAMES, CS_N_TFRAMES, CS_CHUNK_NPK, CS_TUNING_IDX, CS_TF_BASE, CS_OCT_BASE,
+  CS_WS_OCT, CS_PEAK_PITCH, CS_PEAK_MAG, CS_PARTIAL, CS_TP_BASE, CS_XMAX, CS_GPART, CS_OCT_EX, CS_HEAD, CS_COUNT
+};
+struct ChromaLayout {
+  size_t off[CS_COUNT];
+  size_t end;
+};
+static ChromaLayout chroma_layout(int n, int64_t total_len) {
   // octave buffers: < total_len * (1/2 + ... ) + padding; tuning frames <= total_len/512 + n
   const int64_t tfr = total_len / 512 + n;
-  size_t b = 0;
-  b += al256(sizeof(int64_t) * 7 * n) * 2;
-  b += al256(sizeof(int) * n) * 4;
-  b += al256(sizeof(int64_t) * (n + 1)) * 2;
-  b += al256(sizeof(float) * (size_t)(total_len + 64 * 7 * (int64_t)n));
-  b += al256(sizeof(float) * (size_t)tfr * kPeakSlots) * 2;
-  b += al256(sizeof(double) * (size_t)(tfr / CM_FR + n + 1) * 12);
-  b += al256(sizeof(int64_t) * (n + 1));
-  b += al256(sizeof(float) * (size_t)(n + (total_len + 64 * 7 * (int64_t)n) / 256 + 2));
-  b += al256(sizeof(float) * (size_t)tfr * 84);
-  b += al256(sizeof(int) * 7 * n);
-  return b + 4096;
+  const size_t oct_floats = (size_t)(total_len + 64 * 7 * (int64_t)n);
+  size_t bytes[CS_COUNT];
+  bytes[CS_OCT_OFF] = sizeof(int64_t) * 7 * n;
+  bytes[CS_OCT_LEN] = sizeof(int64_t) * 7 * n;
+  bytes[CS_N_FRAMES] = sizeof(int) * n;
+  bytes[CS_N_TFRAMES] = sizeof(int) * n;
+  bytes[CS_CHUNK_NPK] = sizeof(int) * n;
+  bytes[CS_TUNING_IDX] = sizeof(int) * n;
+  bytes[CS_TF_BASE] = sizeof(int64_t) * (n + 1);
+  bytes[CS_OCT_BASE] = sizeof(int64_t) * (n + 1);
+  bytes[CS_WS_OCT] = sizeof(float) * oct_floats;
+  bytes[CS_PEAK_PITCH] = sizeof(float) * (size_t)tfr * kPeakSlots;
+  bytes[CS_PEAK_MAG] = sizeof(float) * (size_t)tfr * kPeakSlots;
+  bytes[CS_PARTIAL] = sizeof(double) * (size_t)(tfr / CM_FR + n + 1) * 12;
+  bytes[CS_TP_BASE] = sizeof(int64_t) * (n + 1);
+  bytes[CS_XMAX] = sizeof(float) * (size_t)(n + oct_floats / 256 + 2);
+  bytes[CS_GPART] = sizeof(float) * (size_t)tfr * 84;
+  bytes[CS_OCT_EX] = sizeof(int) * 7 * n;
+  bytes[CS_HEAD] = (sizeof(float) * 4 + sizeof(int64_t)) * n;  // head [n][4], then cq_off [n]
+  ChromaLayout l;
+  size_t p = 0;
+  for (int i = 0; i < CS_COUNT; ++i) {
+    l.off[i] = p;
+    p += al256(bytes[i]);
+  }
+  l.end = p;
+  return l;
+}
+
+size_t chroma_ws_bytes(int n, int64_t total_len) { return chroma_layout(n, total_len).end + 4096; }
+
+// nc_chroma_workspace_layout: [0] entries written, [1 .. 16] section byte offsets in ChromaSec
+// order, the carved size, the tile constants the stage tests place edges by, then CS_HEAD's offset
+int chroma_ws_layout_query(int n, int64_t total_len, int64_t* out, int cap) {
+  constexpr int kEntries = CS_COUNT + 9;
+  static_assert(kEntries == 26, "include/ncgpu.h, INTEGRATION.md and the message below state 26");
+  if (n <= 0 || total_len < 0 || !out || cap < kEntries) {
+    set_error("chroma layout: needs n_chunks > 0, total_len >= 0 and room for 26 entries");  // kEntries
+    return -2;
+  }
+  const ChromaLayout l = chroma_layout(n, total_len);
+  int k = 0;
+  out[k++] = kEntries;
+  for (int i = 0; i < CS_HEAD; ++i) out[k++] = (int64_t)l.off[i];
+  out[k++] = (int64_t)l.end;
+  out[k++] = D3_TILE;
+  out[k++] = kPeakSlots;
+  out[k++] = CH_FR;
+  out[k++] = C2_FR;
+  out[k++] = C2_NW;
+  out[k++] = CM_FR;
+  out[k++] = kHalfbandK;
+  out[k++] = (int64_t)l.off[CS_HEAD];
+  return k;
 }
 
 int launch_chroma_mean(Context& ctx, const float* sig, const int64_t* chunk_off, const int64_t* chunk_len, int n,
@@ -1486,30 +1562,29 @@ int launch_chroma_mean(Context& ctx, const float* sig, const int64_t* chunk_off,
     set_error("chroma: max_chunk_len must be positive");
     return -2;
   }
-  char* p = static_cast<char*>(ws);
-  auto take = [&](size_t bytes) {
-    char* r = p;
-    p += al256(bytes);
-    return r;
-  };
+  const ChromaLayout lay = chroma_layout(n, total_len);
+  auto sec = [&](ChromaSec s) { return static_cast<char*>(ws) + lay.off[s]; };
   const int64_t tfr = total_len / 512 + n;
   ChromaWs w;
-  w.oct_off = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * 7 * n));
-  w.oct_len = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * 7 * n));
-  w.n_frames = reinterpret_cast<int*>(take(sizeof(int) * n));
-  w.n_tframes = reinterpret_cast<int*>(take(sizeof(int) * n));
-  w.chunk_npk = reinterpret_cast<int*>(take(sizeof(int) * n));
-  w.tuning_idx = out_tuning_idx ? out_tuning_idx : reinterpret_cast<int*>(take(sizeof(int) * n));
-  w.tf_base = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * (n + 1)));
-  w.oct_base = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * (n + 1)));
-  w.ws_oct = reinterpret_cast<float*>(take(sizeof(float) * (size_t)(total_len + 64 * 7 * (int64_t)n)));
-  w.peak_pitch = reinterpret_cast<float*>(take(sizeof(float) * (size_t)tfr * kPeakSlots));
-  w.peak_mag = reinterpret_cast<float*>(take(sizeof(float) * (size_t)tfr * kPeakSlots));
-  w.partial = reinterpret_cast<double*>(take(sizeof(double) * (size_t)(tfr / CM_FR + n + 1) * 12));
-  int64_t* tp_base = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * (n + 1)));
-  w.xmax = reinterpret_cast<float*>(take(sizeof(float) * (size_t)(n + (total_len + 64 * 7 * (int64_t)n) / 256 + 2)));
-  w.gpart = reinterpret_cast<float*>(take(sizeof(float) * (size_t)tfr * 84));
-  w.oct_ex = reinterpret_cast<int*>(take(sizeof(int) * 7 * n));
+  w.oct_off = reinterpret_cast<int64_t*>(sec(CS_OCT_OFF));
+  w.oct_len = reinterpret_cast<int64_t*>(sec(CS_OCT_LEN));
+  w.n_frames = reinterpret_cast<int*>(sec(CS_N_FRAMES));
+  w.n_tframes = reinterpret_cast<int*>(sec(CS_N_TFRAMES));
+  w.chunk_npk = reinterpret_cast<int*>(sec(CS_CHUNK_NPK));
+  // (the workspace's slot stays reserved when the caller gives its own array)
+  w.tuning_idx = out_tuning_idx ? out_tuning_idx : reinterpret_cast<int*>(sec(CS_TUNING_IDX));
+  w.tf_base = reinterpret_cast<int64_t*>(sec(CS_TF_BASE));
+  w.oct_base = reinterpret_cast<int64_t*>(sec(CS_OCT_BASE));
+  w.ws_oct = reinterpret_cast<float*>(sec(CS_WS_OCT));
+  w.peak_pitch = reinterpret_cast<float*>(sec(CS_PEAK_PITCH));
+  w.peak_mag = reinterpret_cast<float*>(sec(CS_PEAK_MAG));
+  w.partial = reinterpret_cast<double*>(sec(CS_PARTIAL));
+  int64_t* tp_base = reinterpret_cast<int64_t*>(sec(CS_TP_BASE));
+  w.xmax = reinterpret_cast<float*>(sec(CS_XMAX));
+  w.gpart = reinterpret_cast<float*>(sec(CS_GPART));
+  w.oct_ex = reinterpret_cast<int*>(sec(CS_OCT_EX));
+  w.head = reinterpret_cast<float*>(sec(CS_HEAD));
+  w.cq_off = reinterpret_cast<int64_t*>(sec(CS_HEAD) + sizeof(float) * 4 * n);
   if (ext) {  // the caller's lists (zeroed counts): the window stage appends to them too
     w.peak_pitch = ext_pitch;
     w.peak_mag = ext_mag;
@@ -1519,7 +1594,7 @@ int launch_chroma_mean(Context& ctx, const float* sig, const int64_t* chunk_off,
   {
     MarkSpan ms_(ctx, "chroma_plan", st);
     hipLaunchKernelGGL(chroma_plan_kernel, dim3(1), dim3(256), 0, st, chunk_len, n, w.oct_off, w.oct_len, w.n_frames,
-                       w.n_tframes, w.tf_base, w.oct_base, tf_skip, tp_base);
+                       w.n_tframes, w.tf_base, w.oct_base, tf_skip, tp_base, sig, chunk_off, w.head, w.cq_off);
     if (!ext) NC_HIP(hipMemsetAsync(w.chunk_npk, 0, sizeof(int) * n, st));
   }
   // grids are sized by the longest chunk; blocks past a chunk's own length exit.  (Forking
@@ -1578,7 +1653,7 @@ int launch_chroma_mean(Context& ctx, const float* sig, const int64_t* chunk_off,
   }
   CqmArgs ma;
   ma.sig = sig;
-  ma.chunk_off = chunk_off;
+  ma.chunk_off = w.cq_off;
   ma.oct_off = w.oct_off;
   ma.oct_len = w.oct_len;
   ma.n_frames = w.n_frames;

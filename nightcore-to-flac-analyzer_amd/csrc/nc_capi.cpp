@@ -41,6 +41,7 @@ int launch_trim(Context& ctx, const float* sig, const int64_t* file_off, const i
                 size_t ws_bytes, hipStream_t st);
 
 size_t chroma_ws_bytes(int n, int64_t total_len);
+int chroma_ws_layout_query(int n, int64_t total_len, int64_t* out, int cap);
 int launch_chroma_mean(Context& ctx, const float* sig, const int64_t* chunk_off, const int64_t* chunk_len, int n,
                        int64_t total_len, int64_t max_chunk_len, float* out_chroma, float* out_tuning,
                        int* out_tuning_idx, int* out_tuning_margin, const int* tf_skip, int64_t tf_skip_total,
@@ -346,6 +347,11 @@ int nc_ibi_from_beats(nc_ctx* ctx, const int* beats, const int64_t* off, const i
 size_t nc_chroma_workspace_bytes(const nc_ctx* ctx, int n_chunks, int64_t total_len) {
   (void)ctx;
   return nc::chroma_ws_bytes(n_chunks, total_len);
+}
+
+int nc_chroma_workspace_layout(const nc_ctx* ctx, int n_chunks, int64_t total_len, int64_t* out, int cap) {
+  (void)ctx;
+  return nc::chroma_ws_layout_query(n_chunks, total_len, out, cap);
 }
 
 int nc_chroma_mean(nc_ctx* ctx, const float* sig, const int64_t* chunk_off, const int64_t* chunk_len, int n_chunks,

@@ -46,6 +46,7 @@ SIGNATURES = {
     "nc_tempo_prior": (I32, [P, P, P, P, P, P, P, P, I32, P, P]),
     "nc_ibi_from_beats": (I32, [P, P, P, P, I32, I32, I32, P, P, P]),
     "nc_chroma_workspace_bytes": (SZ, [P, I32, I64]),
+    "nc_chroma_workspace_layout": (I32, [P, I32, I64, P, I32]),
     "nc_chroma_mean": (I32, [P, P, P, P, I32, I64, I64, P, P, P, P, P, SZ, P]),
     "nc_chroma_lag": (I32, [P, P, P, P, I32, P, P]),
     "nc_chroma_lag_margin": (I32, [P, P, P, P, I32, P, P, P]),

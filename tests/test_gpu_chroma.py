@@ -220,12 +220,18 @@ def test_chroma_short_chunks_between_long_ones_equal_alone(case):
 
 
 def test_chroma_ragged_chunks_across_decimator_tiles(gpu_ctx):
-    """The fused octave chain (cqt.hip decimate3_kernel) owns 2048 level-0 samples per tile:
-    chunk lengths one sample either side of a tile edge and at odd offsets (no aligned
-    float4 path) must give the oracle's chroma like the 20 s chunks do."""
+    """The fused octave chain (cqt.hip decimate3_kernel) owns 8 D3_TILE level-0 samples per
+    workgroup for levels 1-3 and 64 D3_TILE for levels 4-6 (D3_TILE from
+    nc_chroma_workspace_layout; 476 since round 5, so 3 808 and 30 464 samples): chunk lengths
+    one sample either side of those tile edges and at odd offsets (no aligned float4 path)
+    must give the oracle's chroma like the 20 s chunks do.  The first four lengths are the
+    multiples of 2048 the test had when a tile was 2048 samples."""
+    import chroma_stage_cases
+    d3 = chroma_stage_cases.constants()["D3_TILE"]
     nc, src = synth.make_pair(30.0, 1003)
     sig = np.concatenate([src, nc]).astype(np.float32)
-    chunks = [(1, 2048 * 40 + 1), (3, 2048 * 41 - 1), (len(src) + 5, 2048 * 64), (len(src) + 2, 2048 * 48 + 2047)]
+    chunks = [(1, 2048 * 40 + 1), (3, 2048 * 41 - 1), (len(src) + 5, 2048 * 64), (len(src) + 2, 2048 * 48 + 2047),
+              (7, 8 * d3 * 21 - 1), (len(src) + 9, 8 * d3 * 21 + 1), (11, 64 * d3 - 1), (len(src) + 200004, 64 * d3 + 1)]
     got, tun, _, tidx = _chroma_gpu(gpu_ctx, sig, chunks)
     mg = _chroma_gpu.margin
     for i, (o, L) in enumerate(chunks):
