@@ -630,6 +630,53 @@ int nc_melodia_salience(nc_ctx* ctx, const float* sig, const int64_t* file_off, 
                         const float* win, int sal_min_bin, int* pk_count, int* pk_bin, float* pk_sal,
                         void* stream);
 
+/* -------------------------------------------------------------------------
+ * FLAC decode — what the reference gets from librosa.load / soundfile for its FLAC
+ * inputs (io.py:44-55).  Native FLAC streams (RFC 9639): 1-8 channels, 4-24 bits per
+ * sample, block sizes 1 .. 65535, fixed or variable block size; no Ogg container, no
+ * 32-bit samples.  The host walks the container, the device decodes the frames.
+ *
+ * nc_flac_index (host only, no context; every pointer is HOST memory): skips an ID3v2
+ *     tag, requires "fLaC", reads STREAMINFO, skips the other metadata blocks and
+ *     lists the frames.  A frame is a header that parses fully (no reserved code,
+ *     CRC-8 right, sample size and channel count those of STREAMINFO) and whose frame
+ *     or sample number continues the chain from 0, so sync patterns inside a payload
+ *     are passed over.
+ *       info[8]   = rate, channels, bits per sample, total samples per channel (from
+ *                   the frames when STREAMINFO holds 0), min block, max block, byte
+ *                   offset of the first frame, 0
+ *       md5[16]   = STREAMINFO's MD5 (nullable)
+ *       frames    = [cap][8]: byte start, byte end (the next frame's start, or n_bytes),
+ *                   first sample, block size, channel assignment (0-7 independent,
+ *                   8 left/side, 9 side/right, 10 mid/side), bits per sample, header
+ *                   bytes (CRC-8 included), 0 (the file index of a batched decode)
+ *       *n_frames = frames found.  cap = 0 (frames may be NULL) only counts.
+ *     Status: -1 bad argument, -2 not a stream this decodes (Ogg, no marker, 32-bit or
+ *     under 4 bits), -3 cap too small, -4 damaged or truncated (also: the frames do not
+ *     add up to STREAMINFO's total).  Reads never leave data[0 .. n_bytes).
+ * nc_flac_decode: the frames of several files in one launch, one wave per frame.
+ *     data: the files' bytes in one device buffer, 4-byte aligned, data_bytes a
+ *     multiple of 4 and at least 8 beyond the last frame's end.  frames: device
+ *     int64 [n_frames][8] as above with byte offsets into data and column 7 the file.
+ *     files: device int64 [n_files][8] = out_off, channel stride, channels, bits per
+ *     sample, total samples, mono_off (-1: no mix), 0, 0.  Channel c of a file is
+ *       pcm[out_off + c stride + i]      int32 sample (required; also the work space)
+ *       pcm_f32[the same]                sample / 2^(bits-1), exact (nullable)
+ *       mono[mono_off + i]               the sample (1 channel) or f32(a + b) 0.5
+ *                                        (2 channels); nullable
+ *     pcm_len / mono_len: the buffers' lengths in samples; a table row that would
+ *     store outside them is refused.  status: device int [n_frames]: 0 ok, 1 CRC-16
+ *     mismatch, 2 the bitstream ran past the frame's end, 3 reserved or invalid
+ *     field (or table row), 4 decoded length differs from the block size.  A frame
+ *     with status 2-4 leaves its samples undefined.  No workspace, no host
+ *     synchronisation.
+ * ------------------------------------------------------------------------- */
+int nc_flac_index(const uint8_t* data, int64_t n_bytes, int64_t* info, uint8_t* md5, int64_t* frames, int64_t cap,
+                  int64_t* n_frames);
+int nc_flac_decode(nc_ctx* ctx, const uint8_t* data, int64_t data_bytes, const int64_t* frames, int64_t n_frames,
+                   const int64_t* files, int n_files, int32_t* pcm, float* pcm_f32, int64_t pcm_len, float* mono,
+                   int64_t mono_len, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,9 @@ int launch_collect_valid(const double* bpm, const int* nbeats, const uint8_t* ac
                          int n_groups, int min_beats, double* out_values, int* out_n, hipStream_t st);
 int launch_pitch_hz(const int* lags, int n, double* shift_out, double* nc_hz, double* src_hz, hipStream_t st);
 int launch_window_energy(const float* sig, const int64_t* off, int n, int win_len, double* out, hipStream_t st);
+int launch_flac_decode(const uint8_t* data, int64_t data_bytes, const int64_t* frames, int64_t n_frames,
+                       const int64_t* files, int n_files, int* pcm, float* f32, int64_t pcm_len, float* mono,
+                       int64_t mono_len, int* status, hipStream_t st);
 
 }  // namespace nc
 
@@ -609,6 +612,16 @@ int nc_pcm16_to_f32(nc_ctx* ctx, const int16_t* x, int64_t n, float* y, void* st
   CHECK_CTX(ctx);
   SET_DEVICE(ctx);
   return nc::launch_pcm16_to_f32(x, n, y, (hipStream_t)stream);
+}
+
+int nc_flac_decode(nc_ctx* ctx, const uint8_t* data, int64_t data_bytes, const int64_t* frames, int64_t n_frames,
+                   const int64_t* files, int n_files, int32_t* pcm, float* pcm_f32, int64_t pcm_len, float* mono,
+                   int64_t mono_len, int* status, void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  nc::MarkSpan ms_(ctx->c, "flac_decode", (hipStream_t)stream);
+  return nc::launch_flac_decode(data, data_bytes, frames, n_frames, files, n_files, pcm, pcm_f32, pcm_len, mono,
+                                mono_len, status, (hipStream_t)stream);
 }
 
 int nc_speed_out_len(double factor, const int64_t* n_in, int n_files, int64_t* p_out, int64_t* n_out) {

@@ -91,6 +91,8 @@ SIGNATURES = {
     "nc_pv_scan": (I32, [P, P, P, P, I32, I64, I64, P, P, SZ, P]),
     "nc_pv_synth": (I32, [P, P, P, P, P, I32, I64, I64, I64, P, SZ, P, P, P, P]),
     "nc_pv_stretch": (I32, [P, P, P, P, P, I32, I64, I64, I64, I64, P, P, P, P, P, SZ, P]),
+    "nc_flac_index": (I32, [P, I64, P, P, P, I64, C.POINTER(I64)]),
+    "nc_flac_decode": (I32, [P, P, I64, P, I64, P, I32, P, P, I64, P, I64, P, P]),
 }
 
 

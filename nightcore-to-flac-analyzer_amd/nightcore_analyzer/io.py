@@ -1,12 +1,17 @@
 """Audio I/O, windowing, energy gating and silence stripping
 (drop-in for the reference's nightcore_analyzer/io.py).
 
-* ``load_audio`` (io.py:44-55) decodes on the CPU — file decode is out of the
-  engine's scope (north_star); WAV (PCM 8/16/24/32-bit, IEEE float, plain or
-  WAVE_FORMAT_EXTENSIBLE) and ``.npy`` are parsed with numpy, down-mixed to mono float32 and, if
-  the file is not at 22 050 Hz, resampled on the GPU by ``nc_resample_poly``
-  (bit-identical to scipy.signal.resample_poly; the reference uses librosa.load's
-  soxr_hq, which is absent here — see DESIGN.md).
+* ``load_audio`` (io.py:44-55): WAV (PCM 8/16/24/32-bit, IEEE float, plain or
+  WAVE_FORMAT_EXTENSIBLE) and ``.npy`` are parsed with numpy on the CPU and down-mixed to mono
+  float32; FLAC (native streams, 1-8 channels, 4-24 bits) is decoded on the GPU: the host
+  only lists the frames (``nc_flac_index``), ``nc_flac_decode`` decodes them one wave per
+  frame and mixes one or two channels to mono in HBM (``device=True`` keeps the result
+  there as a ``DeviceAudio``).  A file that is not at 22 050 Hz is resampled on the GPU by
+  ``nc_resample_poly`` (bit-identical to scipy.signal.resample_poly; the reference uses
+  librosa.load's soxr_hq, which is absent here — see DESIGN.md).  A FLAC file loads to
+  exactly the array a WAV file of the same PCM does.  MP3 and Ogg are not decoded.
+* ``read_flac_channels`` / ``read_audio_channels``: the channel-preserving read of a FLAC file
+  (on the GPU) and the dispatch on the suffix the renderers use.
 * ``strip_silence`` (io.py:58-79) runs ``nc_trim_bounds`` on the GPU.
 * ``slice_windows`` (io.py:82-112) returns views like the reference, with the
   window energies computed by ``nc_window_energy`` on the GPU.
@@ -188,6 +193,76 @@ def read_wav_channels(path) -> tuple[np.ndarray, int, str]:
     return np.ascontiguousarray(x.reshape(-1, ch).T, dtype=np.float32), sr, name
 
 
+def _flac_streaminfo(path) -> tuple[int, int, int, int]:
+    """(rate, channels, bits per sample, total samples or 0) from a FLAC file's first bytes:
+    an optional ID3v2 tag, the ``fLaC`` marker and the STREAMINFO block."""
+    with open(path, "rb") as fh:
+        head = fh.read(10)
+        pos = 0
+        if head[:3] == b"ID3" and len(head) == 10:
+            size = (head[6] & 0x7F) << 21 | (head[7] & 0x7F) << 14 | (head[8] & 0x7F) << 7 | (head[9] & 0x7F)
+            pos = 10 + size + (10 if head[5] & 0x10 else 0)
+        fh.seek(pos)
+        head = fh.read(42)
+    if head[:4] == b"OggS":
+        raise ValueError(f"{path}: Ogg container (Ogg FLAC) is not supported; only native FLAC streams are")
+    if len(head) < 42 or head[:4] != b"fLaC" or head[4] & 0x7F != 0:
+        raise ValueError(f"{path}: not a FLAC stream (no fLaC marker and STREAMINFO block)")
+    packed = int.from_bytes(head[18:26], "big")
+    return packed >> 44, ((packed >> 41) & 7) + 1, ((packed >> 36) & 31) + 1, packed & ((1 << 36) - 1)
+
+
+def read_flac_channels(path, verify_md5: bool = False) -> tuple[np.ndarray, int, str]:
+    """FLAC -> (float32[channels, frames], rate, "pcm<bits>"), decoded on the GPU
+    (``ops.flac_decode_device``): sample k stands for k / 2^(bits-1), the scaling of
+    ``read_wav_channels``, so a FLAC file reads as the WAV file of the same PCM does."""
+    from .engine import get_engine
+    from .ops import flac_decode_device
+    sig, (info,) = flac_decode_device(get_engine(), [Path(path).read_bytes()], names=[str(path)],
+                                      verify_md5=verify_md5)
+    ch, n = info["channels"], info["total"]
+    hy = sig.buf.cpu().numpy()
+    data = np.stack([hy[o:o + n] for o in sig.off[info["first"]:info["first"] + ch]])
+    return np.ascontiguousarray(data, dtype=np.float32), info["rate"], f"pcm{info['bps']}"
+
+
+def read_audio_channels(path) -> tuple[np.ndarray, int, str]:
+    """(float32[channels, frames], rate, sample format) of a WAV or FLAC file, by its suffix."""
+    if Path(path).suffix.lower() == ".flac":
+        return read_flac_channels(path)
+    return read_wav_channels(path)
+
+
+def _load_flac(path: Path, sr: Optional[int], device: bool):
+    """``load_audio`` of a FLAC file: decode and (for one or two channels) the mono mix in
+    one launch, the load-time resampler on the resident result; three and more channels are
+    mixed on the host by ``_read_wav``'s own numpy expression (an 8-channel numpy mean is not
+    a left-to-right sum)."""
+    import math
+    from .engine import DeviceSignals, get_engine
+    from .ops import flac_decode_device, resample_poly_device
+    import torch
+    eng = get_engine()
+    sig, (info,) = flac_decode_device(eng, [path.read_bytes()], names=[str(path)], mono=True)
+    file_sr, ch, n = info["rate"], info["channels"], info["total"]
+    if info["mono"] is not None:
+        y = info["mono"]
+    else:
+        hy = sig.buf.cpu().numpy()
+        x = np.ascontiguousarray(np.stack([hy[o:o + n] for o in sig.off[:ch]]).T).reshape(-1)
+        y = torch.from_numpy(x.reshape(-1, ch).mean(axis=1).astype(np.float32)).to(eng.dev)
+    if sr is None:
+        sr = file_sr
+    if file_sr != sr:
+        g = math.gcd(int(sr), int(file_sr))
+        out = resample_poly_device(eng, DeviceSignals(y, np.zeros(1, np.int64), np.array([n], np.int64)),
+                                   int(sr) // g, int(file_sr) // g)
+        y = out.buf[:int(out.length[0])]
+    if device:
+        return DeviceAudio(y, sr), sr
+    return np.ascontiguousarray(y.cpu().numpy(), dtype=np.float32), sr
+
+
 def quantize_pcm16(x: np.ndarray) -> tuple[np.ndarray, int]:
     """(int16 clamp(rint(x 32768), -32768, 32767), samples clamped): the host statement of
     ``nc_f32_to_pcm16`` (round half to even; x 32768 is exact in float32)."""
@@ -200,7 +275,7 @@ def write_wav(path, data, sr: int, sample_format: str = "float32") -> None:
     """Write ``data`` ([channels, frames] or [frames]) as a RIFF/WAVE file of 16-bit PCM
     ("pcm16") or IEEE float32 ("float32").  int16 data is written as stored (the renderer
     quantises on the device, ``nc_f32_to_pcm16``); float data going to "pcm16" is quantised
-    here by the same rule (``quantize_pcm16``).  File encode, like decode, stays on the CPU."""
+    here by the same rule (``quantize_pcm16``).  File encode stays on the CPU; the output is WAV."""
     a = np.asarray(data)
     if a.ndim == 1:
         a = a[None, :]
@@ -225,13 +300,18 @@ def write_wav(path, data, sr: int, sample_format: str = "float32") -> None:
     Path(path).write_bytes(head + b"data" + len(body).to_bytes(4, "little") + body)
 
 
-def load_audio(path: str, sr: Optional[int] = SAMPLE_RATE, *, keep_pcm16: bool = False) -> tuple[np.ndarray, int]:
-    """Decode *path* to mono float32 at *sr* Hz (io.py:44-55; decode stays on the CPU).
-    ``sr=None`` keeps the file's own rate (librosa.load(sr=None), spectral.py:52); a .npy
-    file carries no rate and is taken to be at SAMPLE_RATE.  ``keep_pcm16`` (the engine's
-    loaders, pipeline.run): a mono 16-bit WAV already at *sr* is returned as its stored
-    samples (``Pcm16``: the same values as float32 once scaled by 1 / 32768, on the device)."""
+def load_audio(path: str, sr: Optional[int] = SAMPLE_RATE, *, keep_pcm16: bool = False,
+               device: bool = False) -> tuple[np.ndarray, int]:
+    """Decode *path* to mono float32 at *sr* Hz (io.py:44-55; WAV and .npy on the CPU, FLAC on
+    the GPU).  ``sr=None`` keeps the file's own rate (librosa.load(sr=None), spectral.py:52);
+    a .npy file carries no rate and is taken to be at SAMPLE_RATE.  ``keep_pcm16`` (the
+    engine's loaders, pipeline.run): a mono 16-bit WAV already at *sr* is returned as its
+    stored samples (``Pcm16``: the same values as float32 once scaled by 1 / 32768, on the
+    device).  ``device`` (FLAC only): the decoded, mixed and resampled signal stays in HBM and
+    comes back as a ``DeviceAudio``."""
     p = Path(path)
+    if p.suffix.lower() == ".flac":
+        return _load_flac(p, sr, device)
     if p.suffix.lower() == ".npy":
         y, file_sr = np.load(p, allow_pickle=False).astype(np.float32), sr or SAMPLE_RATE
         if y.ndim > 1:
@@ -244,8 +324,8 @@ def load_audio(path: str, sr: Optional[int] = SAMPLE_RATE, *, keep_pcm16: bool =
             y = y.f32()
     else:
         raise NotImplementedError(
-            f"{p.suffix} decoding is outside the engine (the reference uses librosa.load/soundfile, "
-            "not installed here); convert to WAV or .npy first")
+            f"{p.suffix} decoding is not implemented (WAV, FLAC and .npy are; the reference reads the rest "
+            "through librosa.load/soundfile, not installed here); convert to WAV or FLAC first")
     if sr is None:
         sr = file_sr
     if file_sr != sr:                   # io.py:54 resamples at load: on the GPU (nc_resample_poly)
@@ -267,6 +347,16 @@ def decoded_length(x, sr: int = SAMPLE_RATE) -> int:
     if p.suffix.lower() == ".npy":
         a = np.load(p, mmap_mode="r", allow_pickle=False)
         return int(a.shape[1] if a.ndim > 1 else a.shape[0])
+    if p.suffix.lower() == ".flac":            # STREAMINFO alone; the frame index when it holds no total
+        file_sr, _, _, n = _flac_streaminfo(p)
+        if n == 0:
+            from .ops import flac_index
+            n = flac_index(p.read_bytes(), str(p))[0]["total"]
+        if sr is None or file_sr == sr:
+            return n
+        import math
+        g = math.gcd(int(sr), file_sr)
+        return -(-n * (int(sr) // g) // (file_sr // g))
     if p.suffix.lower() != ".wav":
         return len(load_audio(x, sr)[0])          # raises the same NotImplementedError
     size = p.stat().st_size

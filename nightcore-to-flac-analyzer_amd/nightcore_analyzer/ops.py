@@ -253,26 +253,165 @@ def resample_poly(eng: Engine, arrays: Sequence[np.ndarray], up: int, down: int)
     arrays = [np.asarray(a, np.float32) for a in arrays]
     if not arrays:
         return []
-    up, down, h, pre = poly_plan(up, down, max(len(a) for a in arrays))
-    if up == down == 1:
+    if int(up) == int(down):
         return [a.copy() for a in arrays]
-    sig = eng.upload_signals(arrays)
-    n_out = np.array([-(-len(a) * up // down) for a in arrays], np.int64)
-    o_off = np.zeros(len(arrays), np.int64)
+    out = resample_poly_device(eng, eng.upload_signals(arrays), up, down)
+    hy = out.buf.cpu().numpy()
+    return [hy[o:o + n].copy() for o, n in zip(out.off, out.length)]
+
+
+def resample_poly_device(eng: Engine, sig, up: int, down: int):
+    """``resample_poly`` of signals already in HBM (``DeviceSignals``), the result left there
+    (``DeviceSignals``, files back to back): the same launch, no host round trip and no
+    synchronisation.  A 1:1 ratio returns ``sig`` itself."""
+    from .engine import DeviceSignals
+    n = sig.n_files
+    lens = np.asarray(sig.length, np.int64)
+    if n == 0 or int(up) == int(down):
+        return sig
+    up, down, h, pre = poly_plan(up, down, int(lens.max()))
+    n_out = -(-lens * up // down)
+    o_off = np.zeros(n, np.int64)
     o_off[1:] = np.cumsum(n_out)[:-1]
     up_ = _Upload()
     up_.add("in_off", sig.off, np.int64)
-    up_.add("in_len", sig.length, np.int64)
+    up_.add("in_len", lens, np.int64)
     up_.add("out_off", o_off, np.int64)
     up_.add("out_len", n_out, np.int64)
     up_.add("h", h, np.float64)
     d = up_.commit(eng.dev)
     y = torch.empty(max(1, int(n_out.sum())), dtype=torch.float32, device=eng.dev)
-    eng.call("nc_resample_poly", sig.buf.data_ptr(), d["in_off"].data_ptr(), d["in_len"].data_ptr(), len(arrays),
+    eng.call("nc_resample_poly", sig.buf.data_ptr(), d["in_off"].data_ptr(), d["in_len"].data_ptr(), n,
              y.data_ptr(), d["out_off"].data_ptr(), d["out_len"].data_ptr(), int(n_out.max()), d["h"].data_ptr(),
              len(h), up, down, pre, eng.stream())
-    hy = y.cpu().numpy()
-    return [hy[o:o + n].copy() for o, n in zip(o_off, n_out)]
+    return DeviceSignals(y, o_off, n_out)
+
+
+# ------------------------------------------------------------------ FLAC decode (nc_flac_index.cpp + flac.hip)
+FLAC_STATUS = {1: "CRC-16 mismatch", 2: "bitstream ran past the frame's end", 3: "reserved or invalid field",
+               4: "decoded length differs from the block size"}
+
+
+def flac_index(data, name: str = "FLAC data"):
+    """(info dict, int64 frame table [n, 8]) of one FLAC stream's bytes, from the library's host
+    walk ``nc_flac_index`` (needs no device).  info: rate, channels, bps, total (samples per
+    channel), md5 (STREAMINFO's 16 bytes).  The table's columns: byte start, byte end, first
+    sample, block size, channel assignment, bits per sample, header bytes, 0.  ValueError
+    (named after ``name``) for anything that is not a stream the decoder takes."""
+    import ctypes as C
+    from . import _native
+    lib = _native.load()
+    buf = np.frombuffer(bytes(data) or b"\0", np.uint8)
+    n_bytes = len(data)
+    info, md5, n = np.zeros(8, np.int64), np.zeros(16, np.uint8), C.c_int64(0)
+
+    def call(rows, cap):
+        rc = lib.nc_flac_index(buf.ctypes.data, n_bytes, info.ctypes.data, md5.ctypes.data,
+                               rows.ctypes.data if rows is not None else None, cap, C.byref(n))
+        if rc != 0 and not (rc == -3 and rows is not None and cap < n.value):
+            msg = lib.nc_last_error()
+            raise ValueError(f"{name}: {msg.decode() if msg else rc}")
+        return rc
+    cap = max(1024, n_bytes // 256)          # one walk for frames of 256 bytes and more, else a second
+    rows = np.zeros((cap, 8), np.int64)
+    if call(rows, cap) == -3:
+        rows = np.zeros((n.value, 8), np.int64)
+        call(rows, n.value)
+    return (dict(rate=int(info[0]), channels=int(info[1]), bps=int(info[2]), total=int(info[3]), md5=md5.tobytes()),
+            rows[:n.value])
+
+
+def flac_decode_device(eng: Engine, blobs: Sequence[bytes], *, names: Optional[Sequence[str]] = None,
+                       mono: bool = False, verify_md5: bool = False):
+    """Decode the FLAC streams ``blobs`` (the files' bytes) in one upload and one launch
+    (``nc_flac_decode``, one wave per frame): (DeviceSignals, infos).  The DeviceSignals holds
+    every channel of every file as float32 sample / 2^(bps-1) (exact; ``_read_wav``'s scaling),
+    file by file, channel by channel; infos[f] is the index's info dict plus ``first`` (the
+    file's first entry in the DeviceSignals), ``pcm`` (the file's device int32 samples
+    [channels, total]) and, with ``mono`` and one or two channels, ``mono`` (the device float32
+    mix f32(a + b) 0.5, what ``x.reshape(-1, ch).mean(axis=1)`` gives).  A frame whose status
+    is not 0 raises ValueError naming the file, the frame and the reason (this reads the
+    status words back: the one synchronisation).  ``verify_md5`` also downloads the samples
+    and compares their MD5 with STREAMINFO's (skipped when that is all zeros)."""
+    from .engine import DeviceSignals
+    names = [f"FLAC stream {i}" for i in range(len(blobs))] if names is None else [str(n) for n in names]
+    infos, tables, chunks = [], [], []
+    files = np.zeros((max(1, len(blobs)), 8), np.int64)
+    off, length = [], []
+    byte_pos = pcm_len = mono_len = 0
+    for f, blob in enumerate(blobs):
+        info, rows = flac_index(blob, names[f])
+        rows = rows.copy()
+        rows[:, 0:2] += byte_pos
+        rows[:, 7] = f
+        if len(rows) and not np.all(rows[:, 5] == info["bps"]):
+            raise ValueError(f"{names[f]}: the sample size changes inside the stream (unsupported)")
+        tables.append(rows)
+        chunks.append((byte_pos, blob))
+        byte_pos += (len(blob) + 3) // 4 * 4
+        ch, total = info["channels"], info["total"]
+        stride = (total + _ALIGN - 1) // _ALIGN * _ALIGN
+        want_mono = mono and ch <= 2
+        files[f] = (pcm_len, stride, ch, info["bps"], total, mono_len if want_mono else -1, 0, 0)
+        info.update(first=len(off), _out=pcm_len, _stride=stride, _mono=mono_len if want_mono else -1)
+        off += [pcm_len + c * stride for c in range(ch)]
+        length += [total] * ch
+        pcm_len += ch * stride
+        if want_mono:
+            mono_len += stride
+        infos.append(info)
+    frames = np.concatenate(tables) if tables else np.zeros((0, 8), np.int64)
+    host = torch.zeros(byte_pos + 16, dtype=torch.uint8, pin_memory=True)    # 8 bytes of padding and more
+    hv = host.numpy()
+    for pos, blob in chunks:
+        hv[pos:pos + len(blob)] = np.frombuffer(blob, np.uint8)
+    data = host.to(eng.dev, non_blocking=True)
+    up = _Upload()
+    up.add("frames", frames if len(frames) else np.zeros(8), np.int64)
+    up.add("files", files, np.int64)
+    d = up.commit(eng.dev)
+    pcm = torch.zeros(max(_ALIGN, pcm_len), dtype=torch.int32, device=eng.dev)
+    f32 = torch.zeros(max(_ALIGN, pcm_len), dtype=torch.float32, device=eng.dev)
+    mix = torch.zeros(max(_ALIGN, mono_len), dtype=torch.float32, device=eng.dev) if mono else None
+    status = torch.zeros(max(1, len(frames)), dtype=torch.int32, device=eng.dev)
+    if len(frames):
+        eng.call("nc_flac_decode", data.data_ptr(), data.numel(), d["frames"].data_ptr(), len(frames),
+                 d["files"].data_ptr(), len(blobs), pcm.data_ptr(), f32.data_ptr(), pcm_len,
+                 mix.data_ptr() if mix is not None else None, mono_len, status.data_ptr(), eng.stream())
+        bad = np.flatnonzero(status.cpu().numpy()[:len(frames)])
+        if len(bad):
+            g = int(bad[0])
+            f = int(frames[g, 7])
+            k = g - sum(len(t) for t in tables[:f])
+            code = int(status[g].item())
+            raise ValueError(f"{names[f]}: frame {k} (samples {int(frames[g, 2])} .. "
+                             f"{int(frames[g, 2] + frames[g, 3])}): {FLAC_STATUS.get(code, code)}")
+    for f, info in enumerate(infos):
+        o, s, ch, total = info.pop("_out"), info.pop("_stride"), info["channels"], info["total"]
+        info["pcm"] = pcm[o:o + ch * s].view(ch, s)[:, :total]
+        m = info.pop("_mono")
+        info["mono"] = mix[m:m + total] if m >= 0 else None
+        if verify_md5 and info["md5"] != bytes(16):
+            import hashlib
+            width = (info["bps"] + 7) // 8
+            inter = np.ascontiguousarray(info["pcm"].cpu().numpy().T).astype("<i4")
+            got = hashlib.md5(inter.view(np.uint8).reshape(-1, 4)[:, :width].tobytes()).digest()
+            if got != info["md5"]:
+                raise ValueError(f"{names[f]}: MD5 of the decoded samples {got.hex()} differs from STREAMINFO's "
+                                 f"{info['md5'].hex()}")
+    return DeviceSignals(f32, np.asarray(off, np.int64), np.asarray(length, np.int64)), infos
+
+
+def flac_decode(eng: Engine, blobs: Sequence[bytes], **kw) -> List[Tuple[np.ndarray, dict]]:
+    """[(int32 samples [channels, total], info)] of each stream, on the host (``flac_decode_device``)."""
+    _, infos = flac_decode_device(eng, blobs, **kw)
+    out = []
+    for info in infos:
+        info = dict(info)
+        pcm = info.pop("pcm").cpu().numpy()
+        info["mono"] = None if info["mono"] is None else info["mono"].cpu().numpy()
+        out.append((pcm, info))
+    return out
 
 
 # ------------------------------------------------------------------ speed render (speed.hip)

@@ -32,12 +32,15 @@ def _params(window_sec, hop_sec, energy_gate_db, silence_strip_db, src_trim_sec,
 
 def _load(x: PathOrArray, log, what: str, sr: int = 22050):
     """A file decoded as load_audio does (a mono 16-bit WAV kept as its stored samples,
-    io.Pcm16, and widened on the device at upload: half the PCIe bytes), or an array."""
+    io.Pcm16, and widened on the device at upload: half the PCIe bytes; a FLAC file decoded,
+    mixed and resampled on the device and left there, io.DeviceAudio), or an array."""
     log(f"Loading {what} audio…")
     if isinstance(x, DeviceAudio):          # a render already in HBM (render.refine_speed)
         y = x
     elif isinstance(x, np.ndarray):
         y = np.ascontiguousarray(x, dtype=np.float32)
+    elif str(x).lower().endswith(".flac"):
+        y, sr = load_audio(x, sr=sr, device=True)
     else:
         y, sr = load_audio(x, sr=sr, keep_pcm16=True)
     log(f"  {len(y) / sr:.1f} s  ({len(y):,} samples @ {sr} Hz)")

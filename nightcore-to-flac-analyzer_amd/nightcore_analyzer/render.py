@@ -26,7 +26,7 @@ from typing import Callable, List, Optional
 import numpy as np
 
 from .consensus import AnalysisResult
-from .io import DeviceAudio, as_f32, read_wav_channels, write_wav
+from .io import DeviceAudio, as_f32, read_audio_channels, write_wav
 
 Q = 1_000_000            # the six decimals of `sox … speed {F:.6f}` (workflow.py:116)
 MIN_FACTOR, MAX_FACTOR = 0.25, 4.0
@@ -89,7 +89,7 @@ def speed(y: np.ndarray, factor: float, sr: Optional[int] = None) -> np.ndarray:
 
 def speed_file(src_path, dst_path, factor: float, limit_db: Optional[float] = None, *,
                attack_ms: float = 5.0, release_ms: float = 50.0) -> RenderInfo:
-    """Render every channel of the WAV file ``src_path`` at its own rate and write
+    """Render every channel of the WAV or FLAC file ``src_path`` at its own rate and write
     ``dst_path``: a 16-bit PCM source gives a 16-bit PCM file (quantised on the device,
     ``nc_f32_to_pcm16``), anything else a float32 file.  With a ceiling ``limit_db`` (dBFS,
     at most 0) the true-peak limiter (``nc_true_peak_limit``, channels linked) runs on the
@@ -99,7 +99,7 @@ def speed_file(src_path, dst_path, factor: float, limit_db: Optional[float] = No
     f = quantize_factor(factor)
     if limit_db is not None and not float(limit_db) <= 0.0:
         raise ValueError(f"limiter ceiling {limit_db!r} dBFS is above full scale")
-    data, sr, fmt = read_wav_channels(src_path)
+    data, sr, fmt = read_audio_channels(src_path)
     eng = get_engine()
     out, peak_d, P = speed_render_device(eng, list(data), f)
     ch, n_out = data.shape[0], int(out.length[0])
@@ -236,7 +236,7 @@ class PitchInfo(RenderInfo):
 
 def pitch_file(src_path, dst_path, semitones: float, limit_db: Optional[float] = None, *,
                attack_ms: float = 5.0, release_ms: float = 50.0) -> PitchInfo:
-    """Shift every channel of the WAV file ``src_path`` by ``semitones`` at its own rate and
+    """Shift every channel of the WAV or FLAC file ``src_path`` by ``semitones`` at its own rate and
     write ``dst_path`` (same rate, channels and length): a 16-bit PCM source gives a 16-bit PCM
     file (``nc_f32_to_pcm16``), anything else a float32 file.  With a ceiling ``limit_db`` the
     true-peak limiter runs on the resident result first, as in ``speed_file``."""
@@ -245,7 +245,7 @@ def pitch_file(src_path, dst_path, semitones: float, limit_db: Optional[float] =
     ratio = quantize_semitones(semitones)
     if limit_db is not None and not float(limit_db) <= 0.0:
         raise ValueError(f"limiter ceiling {limit_db!r} dBFS is above full scale")
-    data, sr, fmt = read_wav_channels(src_path)
+    data, sr, fmt = read_audio_channels(src_path)
     eng = get_engine()
     out, peak_d, P = pitch_shift_device(eng, list(data), semitones)
     ch, n_out = data.shape[0], int(data.shape[1])
