@@ -35,6 +35,7 @@ import torch
 
 from . import _native
 from . import consensus as C
+from . import launch
 
 SR = 22050
 HOP_LENGTH = 512
@@ -499,7 +500,7 @@ def plan_batch(off: np.ndarray, length: np.ndarray, start: np.ndarray, end: np.n
                align: Optional[List[Tuple[float, float]]] = None) -> BatchPlan:
     """Silence-trim bounds [start, end) of every file -> BatchPlan (host only, deterministic:
     every rank of a sharded run derives the same plan)."""
-    if 1 + int(p.window_sec * SR) // HOP_LENGTH > MAX_WINDOW_FRAMES:
+    if launch.frames_of(int(p.window_sec * SR), HOP_LENGTH) > MAX_WINDOW_FRAMES:
         raise ValueError(f"window_sec={p.window_sec} is longer than the engine's per-window stage supports "
                          f"({(MAX_WINDOW_FRAMES - 1) * HOP_LENGTH / SR:.0f} s)")
     nF = len(off)
@@ -943,13 +944,9 @@ class Engine:
         d = up.commit(dev)
         n = len(jobs)
         out = torch.empty(3 * n, dtype=torch.float64, device=dev)
-        ws = self.workspace(ws_tag + "boot", tot)
-        il, gl, ih, gh = percentile_params(n_boot, ci)
-        self.call("nc_bootstrap_ratio", d["vals"].data_ptr(), d["a_off"].data_ptr(), d["a_n"].data_ptr(),
-                  d["b_off"].data_ptr() if has_b else None, d["b_n"].data_ptr() if has_b else None, n,
-                  n_boot, d["seed"].data_ptr(), il, gl, ih, gh, 1, out[0:n].data_ptr(),
-                  out[n:2 * n].data_ptr(), out[2 * n:3 * n].data_ptr(), None, d["wsoff"].data_ptr(),
-                  d["cap"].data_ptr(), ws.data_ptr(), ws.numel(), self.stream())
+        launch.bootstrap_ratio(self, d["vals"], d["a_off"], d["a_n"], d["b_off"] if has_b else None,
+                               d["b_n"] if has_b else None, n, d["seed"], percentile_params(n_boot, ci), 1, out,
+                               d["wsoff"], d["cap"], ws_tag + "boot", tot, n_boot=n_boot)
         o = out.cpu().numpy()
         return [(float(o[i]), (float(o[n + i]), float(o[2 * n + i]))) for i in range(n)]
 
@@ -1159,11 +1156,11 @@ class Engine:
         pair, outcomes)`` runs as each group is assembled, while the later groups are still on
         the device (the sharded result gather packs its records there).  Returns the results."""
         hs = self.host_stats
-        launch = torch.cuda.current_stream(self.dev)
+        cur = torch.cuda.current_stream(self.dev)
         # the signals are complete on the launch stream here; trims of later batches wait for
         # this point only, not for the groups queued on the launch stream after it
         ev_sig = torch.cuda.Event()
-        ev_sig.record(launch)
+        ev_sig.record(cur)
         results: List[List[PairOutcome]] = [[] for _ in batches]
         # up to GROUPS_IN_FLIGHT groups (of any batch) are queued before the host waits for the
         # oldest: the window stream never idles behind the host assembly of an earlier group,
@@ -1179,7 +1176,7 @@ class Engine:
             if not self._split_trim(signals, p, groups):
                 return groups, []
             nF, f1 = signals.n_files, 2 * groups[0][1]
-            return groups, [self._trim_launch(signals, 0, f1, p, self.trim_stream if ahead else launch, ev_sig),
+            return groups, [self._trim_launch(signals, 0, f1, p, self.trim_stream if ahead else cur, ev_sig),
                             self._trim_launch(signals, f1, nF, p, self.trim_stream if ahead else self.tail_stream,
                                               ev_sig)]
 
@@ -1255,11 +1252,11 @@ class Engine:
         side stream the trim first waits for ev_sig (the signals complete on the launch stream)."""
         dev, n = self.dev, f1 - f0
         lens = np.ascontiguousarray(signals.length[f0:f1], np.int64)
-        launch = torch.cuda.current_stream(dev)
-        if stream != launch:          # the signals may still be in flight on the launch stream
+        cur = torch.cuda.current_stream(dev)
+        if stream != cur:          # the signals may still be in flight on the launch stream
             if ev_sig is None:
                 ev_sig = torch.cuda.Event()
-                ev_sig.record(launch)
+                ev_sig.record(cur)
             stream.wait_event(ev_sig)
         with torch.cuda.stream(stream):
             up = _Upload()
@@ -1323,7 +1320,7 @@ class Engine:
         jobs) in one H2D copy -> (device spans, sizes).  ``trim_file``: its first file within its trim."""
         B, w0, w1, n_win, n_src_w, f_len = pl.B, pl.w0, pl.w1, pl.n_win, pl.n_src_w, pl.f_len
         pair_chunks, n_chunks, n_cp = pl.pair_chunks, pl.n_chunks, pl.n_cp
-        T, acw = 1 + pl.win_n // HOP_LENGTH, int(int(8.0 * SR) // HOP_LENGTH)
+        T, acw = launch.frames_of(pl.win_n, HOP_LENGTH), launch.tempogram_window(SR, HOP_LENGTH)
         # shared tuning frames: a standard 20 s chunk that starts where a window of the same file
         # starts has its first tp tuning frames in that window's STFT (nc_window_stage_tuning)
         tp = (pl.win_n - 1024) // HOP_LENGTH + 1 if pl.win_n >= 1024 else 0
@@ -1418,60 +1415,36 @@ class Engine:
         n_win, win_n = pl.n_win, pl.win_n
         if not n_win:
             return None, None
-        dev, st = self.dev, self.stream()
-        onset = torch.empty(n_win * dm.T, dtype=torch.float32, device=dev)
-        tg = torch.empty(n_win * dm.acw, dtype=torch.float64, device=dev)
-        ws = self.workspace("win", self.ctx.lib.nc_window_stage_workspace_bytes(self.ctx.h, n_win, win_n, HOP_LENGTH))
         # window energies (io._rms_db): from the silence trim's f64 block sums when the batch
         # was trimmed (the STFT then skips its per-frame energy), else fused into the STFT
-        en_ptr = o["energy"].data_ptr()
+        energy = o["energy"]
         if trim is not None:
-            trim.window_energies(d["win_off"], d["win_file"], n_win, win_n, en_ptr)
-            en_ptr = None
-        if dm.share:
-            self.call("nc_window_stage_tuning", signals.buf.data_ptr(), d["win_off"].data_ptr(), None, n_win,
-                      win_n, HOP_LENGTH, onset.data_ptr(), tg.data_ptr(), en_ptr,
-                      d["win_chunk"].data_ptr(), d["tf_base"].data_ptr(), dm.tp, peaks[0].data_ptr(),
-                      peaks[1].data_ptr(), o["npk"].data_ptr(), ev_stft.cuda_event, ws.data_ptr(), ws.numel(), st)
-        else:
-            self.call("nc_window_stage", signals.buf.data_ptr(), d["win_off"].data_ptr(), None, n_win, win_n,
-                      HOP_LENGTH, onset.data_ptr(), tg.data_ptr(), en_ptr, ws.data_ptr(), ws.numel(), st)
-        return onset, tg
+            trim.window_energies(d["win_off"], d["win_file"], n_win, win_n, energy.data_ptr())
+            energy = None
+        tuning = (d["win_chunk"], d["tf_base"], dm.tp, *peaks, o["npk"], ev_stft) if dm.share else None
+        return launch.window_stage(self, signals.buf, d["win_off"], n_win, win_n, HOP_LENGTH, SR, energy=energy,
+                                   tuning=tuning)[:2]
 
     def _group_chroma(self, signals: DeviceSignals, pl: BatchPlan, d, o, dm: _Dims, peaks, ev_stft,
                       stage_copy: "_StageCopies") -> torch.cuda.Event:
         """The chroma chain on stream 2: chunk chroma and tuning, pair lags, pitch, and the
         chunk-shift bootstrap (pitch.py:143-150, seed 0), which needs nothing else -> its event."""
         s2 = self.chroma_stream
-        st2 = s2.cuda_stream
         n_chunks, n_cp, chunk_len, npj = pl.n_chunks, pl.n_cp, pl.chunk_len, dm.n_pitch_jobs
         pvals = o["vals"][dm.TV:]
         if n_chunks:
-            tot_len = int(np.sum(chunk_len))
-            ws_c = self.workspace("chroma", self.ctx.lib.nc_chroma_workspace_bytes(self.ctx.h, n_chunks, tot_len))
-            ws_c.record_stream(s2)  # used on stream 2: not reusable until that work is done
-            if dm.share:
-                self.call("nc_chroma_mean_shared", signals.buf.data_ptr(), d["chunk_off"].data_ptr(),
-                          d["chunk_len"].data_ptr(), n_chunks, tot_len, int(max(chunk_len)), o["chroma"].data_ptr(),
-                          o["tuning"].data_ptr(), None, o["tmargin"].data_ptr(), d["tf_skip"].data_ptr(),
-                          dm.n_shared, peaks[0].data_ptr(), peaks[1].data_ptr(), o["npk"].data_ptr(),
-                          ev_stft.cuda_event, ws_c.data_ptr(), ws_c.numel(), st2)
-            else:
-                self.call("nc_chroma_mean", signals.buf.data_ptr(), d["chunk_off"].data_ptr(),
-                          d["chunk_len"].data_ptr(), n_chunks, tot_len, int(max(chunk_len)), o["chroma"].data_ptr(),
-                          o["tuning"].data_ptr(), None, o["tmargin"].data_ptr(), ws_c.data_ptr(), ws_c.numel(), st2)
-            self.call("nc_chroma_lag_margin", o["chroma"].data_ptr(), d["lag_src"].data_ptr(),
-                      d["lag_nc"].data_ptr(), n_cp, o["clag"].data_ptr(), o["cmargin"].data_ptr(), st2)
+            # the launchers record stream 2 on their workspaces: not reusable until that work is done
+            shared = (d["tf_skip"], dm.n_shared, *peaks, o["npk"], ev_stft) if dm.share else None
+            launch.chroma_mean(self, signals.buf, d["chunk_off"], d["chunk_len"], n_chunks, int(np.sum(chunk_len)),
+                               int(max(chunk_len)), chroma=o["chroma"], tuning=o["tuning"], tmargin=o["tmargin"],
+                               shared=shared, stream=s2)
+            launch.chroma_lag_margin(self, o["chroma"], d["lag_src"], d["lag_nc"], n_cp, lag=o["clag"],
+                                     margin=o["cmargin"], stream=s2)
             self.call("nc_pitch_hz", o["clag"].data_ptr(), n_cp, pvals[0:n_cp].data_ptr(),
-                      pvals[n_cp:2 * n_cp].data_ptr(), pvals[2 * n_cp:3 * n_cp].data_ptr(), st2)
+                      pvals[n_cp:2 * n_cp].data_ptr(), pvals[2 * n_cp:3 * n_cp].data_ptr(), s2.cuda_stream)
         if npj:
-            sout = o["sout"]
-            ws2 = self.workspace("boot_s", dm.shift_bytes)
-            ws2.record_stream(s2)
-            self.call("nc_bootstrap_ratio", o["vals"].data_ptr(), d["s_off"].data_ptr(), d["s_n"].data_ptr(), None,
-                      None, npj, C.N_BOOTSTRAP, d["s_seed"].data_ptr(), *_BOOT_PCT, MIN_CHUNKS,
-                      sout[0:npj].data_ptr(), sout[npj:2 * npj].data_ptr(), sout[2 * npj:3 * npj].data_ptr(), None,
-                      d["s_wsoff"].data_ptr(), d["s_cap"].data_ptr(), ws2.data_ptr(), ws2.numel(), st2)
+            launch.bootstrap_ratio(self, o["vals"], d["s_off"], d["s_n"], None, None, npj, d["s_seed"], _BOOT_PCT,
+                                   MIN_CHUNKS, o["sout"], d["s_wsoff"], d["s_cap"], "boot_s", dm.shift_bytes, stream=s2)
         stage_copy("pitch", s2, ["clag", "cmargin", ("vals", dm.TV, dm.TV + dm.PV), "sout", "chroma", "tuning",
                                  "tmargin"])
         ev_chroma = torch.cuda.Event()
@@ -1481,39 +1454,32 @@ class Engine:
     def _group_tempo(self, pl: BatchPlan, p: Params, d, o, dm: _Dims, onset, tg, stage_copy: "_StageCopies") -> None:
         """The tempo chain on the launch stream: energy gate, source beats (prior 120), the
         pairs' priors, nightcore beats, and the valid tempos compacted into the bootstrap jobs."""
-        s1, st = torch.cuda.current_stream(self.dev), self.stream()
+        s1 = torch.cuda.current_stream(self.dev)
+        st = s1.cuda_stream
         B, n_win, n_src_w, T, acw = pl.B, pl.n_win, pl.n_src_w, dm.T, dm.acw
-        bpm, lag, nbeats, margin = o["bpm"], o["lag"], o["nbeats"], o["margin"]
+        res = bpm, lag, nbeats, margin = o["bpm"], o["lag"], o["nbeats"], o["margin"]
         prior, active, tvals = o["prior"], o["active"], o["vals"][:dm.TV]
         if not n_win:
             prior.fill_(120.0)
             stage_copy("gate", s1, ["prior"])
             return
         # windows longer than ~66 s do not fit the beat tracker's LDS path: global workspace
-        bws, bws_n, btot = None, 0, 0
-        if beat_needs_workspace(T, acw):
-            wsb = self.workspace("beats", self.ctx.lib.nc_tempo_beats_workspace_bytes(n_win * T))
-            bws, bws_n, btot = wsb.data_ptr(), wsb.numel(), n_win * T
+        btot = n_win * T if beat_needs_workspace(T, acw) else 0
         self.call("nc_energy_gate", o["energy"].data_ptr(), d["w0"].data_ptr(), d["w1"].data_ptr(), pl.nF,
                   float(p.energy_gate_db), active.data_ptr(), st)
         stage_copy("gate", s1, ["energy", "active"])
         if n_src_w:
-            self.call("nc_tempo_beats", onset.data_ptr(), d["on_off"].data_ptr(), d["on_len"].data_ptr(),
-                      n_src_w, T, tg.data_ptr(), acw, d["start120"].data_ptr(), d["src_pair"].data_ptr(),
-                      active.data_ptr(), HOP_LENGTH, 1, bpm.data_ptr(), lag.data_ptr(), nbeats.data_ptr(),
-                      margin.data_ptr(), None, btot, bws, bws_n, st)
+            launch.tempo_beats(self, onset, d["on_off"], d["on_len"], n_src_w, T, tg, acw, d["start120"], HOP_LENGTH,
+                               prior_idx=d["src_pair"], active=active, out=res, total=btot, st=st)
         self.call("nc_tempo_prior", bpm.data_ptr(), nbeats.data_ptr(), active.data_ptr(),
                   d["src_w0"].data_ptr(), d["src_w1"].data_ptr(), d["src_len"].data_ptr(),
                   d["nc_len"].data_ptr(), B, prior.data_ptr(), st)
         stage_copy("src", s1, [("bpm", 0, n_src_w), ("nbeats", 0, n_src_w), ("margin", 0, n_src_w), "prior"])
         n_nc_w = n_win - n_src_w
         if n_nc_w:
-            self.call("nc_tempo_beats", onset.data_ptr(),
-                      d["on_off"][n_src_w:].data_ptr(), d["on_len"][n_src_w:].data_ptr(), n_nc_w, T,
-                      tg[n_src_w * acw:].data_ptr(), acw, prior.data_ptr(), d["nc_pair"].data_ptr(),
-                      active[n_src_w:].data_ptr(), HOP_LENGTH, 1, bpm[n_src_w:].data_ptr(),
-                      lag[n_src_w:].data_ptr(), nbeats[n_src_w:].data_ptr(), margin[n_src_w:].data_ptr(),
-                      None, btot, bws, bws_n, st)
+            launch.tempo_beats(self, onset, d["on_off"][n_src_w:], d["on_len"][n_src_w:], n_nc_w, T,
+                               tg[n_src_w * acw:], acw, prior, HOP_LENGTH, prior_idx=d["nc_pair"],
+                               active=active[n_src_w:], out=[x[n_src_w:] for x in res], total=btot, st=st)
         stage_copy("nc", s1, [("bpm", n_src_w, n_win), ("nbeats", n_src_w, n_win), ("margin", n_src_w, n_win)])
         # valid-tempo compaction per side: the counts land in the bootstrap jobs' a_n / b_n
         for side, cnt in (("nc", d["a_n"]), ("src", d["b_n"])):
@@ -1530,13 +1496,8 @@ class Engine:
         s3 = self.tail_stream
         s3.wait_event(ev_window)
         s3.wait_event(ev_chroma)
-        nj, bout = dm.nj, o["bout"]
-        ws = self.workspace("boot", dm.boot_bytes)
-        ws.record_stream(s3)
-        self.call("nc_bootstrap_ratio", o["vals"].data_ptr(), d["a_off"].data_ptr(), d["a_n"].data_ptr(),
-                  d["b_off"].data_ptr(), d["b_n"].data_ptr(), nj, C.N_BOOTSTRAP, d["seed"].data_ptr(), *_BOOT_PCT,
-                  C.MIN_VALID, bout[0:nj].data_ptr(), bout[nj:2 * nj].data_ptr(), bout[2 * nj:].data_ptr(), None,
-                  d["wsoff"].data_ptr(), d["cap"].data_ptr(), ws.data_ptr(), ws.numel(), s3.cuda_stream)
+        launch.bootstrap_ratio(self, o["vals"], d["a_off"], d["a_n"], d["b_off"], d["b_n"], dm.nj, d["seed"], _BOOT_PCT,
+                               C.MIN_VALID, o["bout"], d["wsoff"], d["cap"], "boot", dm.boot_bytes, stream=s3)
         with torch.cuda.stream(s3):
             hbuf, host = ar.to_host()
             host["pvals"] = host["vals"][dm.TV:]
@@ -1598,7 +1559,7 @@ class Engine:
         file (tempo.py:158-172); start bpm of file f = start_vals[pidx[f]]."""
         dev, st = self.dev, self.stream()
         nF = len(f_len)
-        frames = 1 + np.asarray(f_len, np.int64) // hop
+        frames = launch.frames_of(np.asarray(f_len, np.int64), hop)
         total = int(frames.sum())
         onset = torch.empty(max(1, total), dtype=torch.float32, device=dev)
         fbase = torch.empty(nF + 1, dtype=torch.int64, device=dev)
@@ -1606,41 +1567,25 @@ class Engine:
         ws = self.workspace(ws_tag + "ibi_on", wsb)
         self.call("nc_ibi_onset", buf.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), nF, total, hop,
                   onset.data_ptr(), fbase.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        acw = int(int(8.0 * self.sr) // hop)
+        acw = launch.tempogram_window(self.sr, hop)
         tg = torch.empty(nF * acw, dtype=torch.float64, device=dev)
         fmax = int(frames.max())
         wsb = self.ctx.lib.nc_ibi_tempogram_workspace_bytes(self.ctx.h, nF, total, fmax, hop)
         ws = self.workspace(ws_tag + "ibi_tg", wsb)
         self.call("nc_ibi_tempogram", onset.data_ptr(), fbase.data_ptr(), nF, total, fmax, hop, tg.data_ptr(),
                   ws.data_ptr(), ws.numel(), st)
-        lens = h2d(frames, np.int32, dev)
-        bpm = torch.zeros(nF, dtype=torch.float64, device=dev)
-        lag = torch.zeros(nF, dtype=torch.int32, device=dev)
-        nb = torch.zeros(nF, dtype=torch.int32, device=dev)
-        mg = torch.zeros(nF, dtype=torch.float64, device=dev)
-        beats = torch.empty(max(1, total), dtype=torch.int32, device=dev)
-        wsb = self.ctx.lib.nc_tempo_beats_workspace_bytes(total)
-        ws = self.workspace(ws_tag + "ibi_beats", wsb)
-        self.call("nc_tempo_beats", onset.data_ptr(), fbase.data_ptr(), lens.data_ptr(), nF, int(frames.max()),
-                  tg.data_ptr(), acw, start_vals.data_ptr(), pidx.data_ptr(), None, hop, 1, bpm.data_ptr(),
-                  lag.data_ptr(), nb.data_ptr(), mg.data_ptr(), beats.data_ptr(), total, ws.data_ptr(), ws.numel(),
-                  st)
-        ibis = torch.empty(max(1, total), dtype=torch.float64, device=dev)
-        nibi = torch.zeros(nF, dtype=torch.int32, device=dev)
-        self.call("nc_ibi_from_beats", beats.data_ptr(), fbase.data_ptr(), nb.data_ptr(), nF, hop, min_ibis,
-                  ibis.data_ptr(), nibi.data_ptr(), st)
+        res = launch.beats_to_ibis(self, onset, fbase, h2d(frames, np.int32, dev), nF, fmax, tg, acw, start_vals, pidx,
+                                   hop, min_ibis, total, ws_tag + "ibi_beats", st=st)
         fb_h = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
-        return dict(onset=onset, fbase=fbase, fbase_h=fb_h, frames=frames, tg=tg, bpm=bpm, lag=lag, nbeats=nb,
-                    margin=mg, beats=beats, ibis=ibis, nibi=nibi)
+        return dict(res, onset=onset, fbase=fbase, fbase_h=fb_h, frames=frames, tg=tg)
 
     def _ibi_pass(self, signals, d_off, d_len, f_len, prior, B, keep_beats=False):
-        dev, st = self.dev, self.stream()
+        dev = self.dev
         nF = 2 * B
         starts = torch.cat([_tensor(prior)[:B], torch.full((1,), 120.0, dtype=torch.float64, device=dev)])
         pidx = h2d([f // 2 if f % 2 == 0 else B for f in range(nF)], np.int32, dev)
         core = self.ibi_core(signals.buf, d_off, d_len, f_len, starts, pidx)
         frames, fb_h, ibis, nibi = core["frames"], core["fbase_h"], core["ibis"], core["nibi"]
-        nb, bpm, lag, mg = core["nbeats"], core["bpm"], core["lag"], core["margin"]
         # bootstrap: A = src ibis, B = nc ibis (consensus.py:303-307), seed 42, need >= 4 each
         caps = [int(frames[2 * b] // 32 + frames[2 * b + 1] // 32 + 4) for b in range(B)]
         wsoff, tot = self._job_offsets(caps)
@@ -1651,18 +1596,12 @@ class Engine:
         up.add("wsoff", wsoff, np.int64)
         up.add("cap", caps, np.int32)
         dd = up.commit(dev)
-        src_i = torch.arange(1, nF, 2, device=dev)
-        nc_i = torch.arange(0, nF, 2, device=dev)
-        a_n = nibi[src_i].contiguous()
-        b_n = nibi[nc_i].contiguous()
+        a_n = nibi[1::2].contiguous()           # the sources' counts
+        b_n = nibi[0::2].contiguous()
         out = torch.full((3 * B,), float("nan"), dtype=torch.float64, device=dev)
-        ws = self.workspace("boot_ibi", tot)
-        il, gl, ih, gh = percentile_params(C.N_BOOTSTRAP, C.CI_LEVEL)
-        self.call("nc_bootstrap_ratio", ibis.data_ptr(), dd["a_off"].data_ptr(), a_n.data_ptr(),
-                  dd["b_off"].data_ptr(), b_n.data_ptr(), B, C.N_BOOTSTRAP, dd["seed"].data_ptr(), il, gl, ih, gh,
-                  4, out[0:B].data_ptr(), out[B:2 * B].data_ptr(), out[2 * B:].data_ptr(), None,
-                  dd["wsoff"].data_ptr(), dd["cap"].data_ptr(), ws.data_ptr(), ws.numel(), st)
-        res = dict(out=out, nibi=nibi, nbeats=nb, bpm=bpm, lag=lag, margin=mg)
+        launch.bootstrap_ratio(self, ibis, dd["a_off"], a_n, dd["b_off"], b_n, B, dd["seed"], _BOOT_PCT, 4, out,
+                               dd["wsoff"], dd["cap"], "boot_ibi", tot)
+        res = dict(out=out, **{k: core[k] for k in ("nibi", "nbeats", "bpm", "lag", "margin")})
         if keep_beats:
             res.update(beats=core["beats"], fbase=fb_h)
         return res

@@ -6,32 +6,46 @@ back in the reference's Python types.
 """
 from __future__ import annotations
 
+import ctypes as C
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from .engine import SR, Engine, _Upload, percentile_params, seed_state
+from . import _native, launch
+from .engine import _ALIGN, SR, DeviceSignals, Engine, Params, _Upload, h2d
 
 HOP = 512
+
+
+def _signals(eng: Engine, src, f32: bool = True) -> DeviceSignals:
+    """``src`` if it is a ``DeviceSignals`` (already in HBM), else its arrays uploaded (``f32``: cast first)."""
+    if isinstance(src, DeviceSignals):
+        return src
+    return eng.upload_signals([np.asarray(a, np.float32) for a in src] if f32 else list(src))
+
+
+def _packed(lengths: np.ndarray) -> Tuple[np.ndarray, int]:
+    """(offsets, total) of outputs of these lengths back to back, each on a 64-sample boundary."""
+    pad = (lengths + _ALIGN - 1) // _ALIGN * _ALIGN
+    off = np.zeros(len(lengths), np.int64)
+    off[1:] = np.cumsum(pad)[:-1]
+    return off, int(pad.sum())
+
+
+def _read_back(buf: torch.Tensor, off, length) -> List[np.ndarray]:
+    """The files of a device buffer as host arrays (one blocking copy of the buffer)."""
+    h = buf.cpu().numpy()
+    return [h[o:o + n].copy() for o, n in zip(off, length)]
 
 
 def trim_bounds(eng: Engine, audios: Sequence[np.ndarray], top_db: float) -> List[Tuple[int, int]]:
     """librosa.effects.trim bounds (io.py:76) for each array."""
     sig = eng.upload_signals(audios)
-    up = _Upload()
-    up.add("off", sig.off, np.int64)
-    up.add("len", sig.length, np.int64)
-    d = up.commit(eng.dev)
-    n = sig.n_files
-    tot = int(np.sum(1 + sig.length // 512))
-    lens = np.ascontiguousarray(sig.length, np.int64)
-    ws = eng.workspace("trim", eng.ctx.lib.nc_trim_workspace_bytes(lens.ctypes.data, n))
-    se = torch.empty(2 * n, dtype=torch.int64, device=eng.dev)
-    eng.call("nc_trim_bounds", sig.buf.data_ptr(), d["off"].data_ptr(), d["len"].data_ptr(), n, tot,
-             float(top_db), se[:n].data_ptr(), se[n:].data_ptr(), ws.data_ptr(), ws.numel(), eng.stream())
-    h = se.cpu().numpy()
-    return [(int(h[i]), int(h[n + i])) for i in range(n)]
+    start, end = eng._trim_launch(sig, 0, sig.n_files, Params(silence_strip_db=top_db),
+                                  torch.cuda.current_stream(eng.dev), pinned=False).bounds()
+    return list(zip(start.tolist(), end.tolist()))
 
 
 def window_energies(eng: Engine, audio: np.ndarray, starts: np.ndarray, win_len: int) -> np.ndarray:
@@ -53,12 +67,11 @@ def window_tempos(eng: Engine, audios: Sequence[np.ndarray], start_bpms: Sequenc
     by_len: dict = {}
     for i, a in enumerate(audios):
         by_len.setdefault(len(a), []).append(i)
-    acw = int(int(8.0 * eng.sr) // HOP)     # the tempogram window of the engine's rate
     for L, idx in by_len.items():
         if L == 0:
             continue
         n = len(idx)
-        T = 1 + L // HOP
+        T = launch.frames_of(L, HOP)
         sig = eng.upload_signals([audios[i] for i in idx])
         up = _Upload()
         up.add("off", sig.off, np.int64)
@@ -66,23 +79,11 @@ def window_tempos(eng: Engine, audios: Sequence[np.ndarray], start_bpms: Sequenc
         up.add("on_len", np.full(n, T), np.int32)
         up.add("start", [start_bpms[i] for i in idx], np.float64)
         d = up.commit(eng.dev)
-        onset = torch.empty(n * T, dtype=torch.float32, device=eng.dev)
-        tg = torch.empty(n * acw, dtype=torch.float64, device=eng.dev)
         en = torch.empty(n, dtype=torch.float64, device=eng.dev)
-        wsb = eng.ctx.lib.nc_window_stage_workspace_bytes(eng.ctx.h, n, L, HOP)
-        ws = eng.workspace("win", wsb)
-        st = eng.stream()
-        eng.call("nc_window_stage", sig.buf.data_ptr(), d["off"].data_ptr(), None, n, L, HOP, onset.data_ptr(),
-                 tg.data_ptr(), en.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        bpm = torch.zeros(n, dtype=torch.float64, device=eng.dev)
-        lag = torch.zeros(n, dtype=torch.int32, device=eng.dev)
-        nb = torch.zeros(n, dtype=torch.int32, device=eng.dev)
-        mg = torch.zeros(n, dtype=torch.float64, device=eng.dev)
-        wsb2 = eng.ctx.lib.nc_tempo_beats_workspace_bytes(n * T)
-        ws2 = eng.workspace("beats", wsb2)
-        eng.call("nc_tempo_beats", onset.data_ptr(), d["on_off"].data_ptr(), d["on_len"].data_ptr(), n, T,
-                 tg.data_ptr(), acw, d["start"].data_ptr(), None, None, HOP, 1, bpm.data_ptr(), lag.data_ptr(),
-                 nb.data_ptr(), mg.data_ptr(), None, n * T, ws2.data_ptr(), ws2.numel(), st)
+        # the tempogram window of the engine's rate
+        onset, tg, T, acw = launch.window_stage(eng, sig.buf, d["off"], n, L, HOP, eng.sr, energy=en)
+        bpm, lag, nb, mg = launch.tempo_beats(eng, onset, d["on_off"], d["on_len"], n, T, tg, acw, d["start"], HOP,
+                                              total=n * T)
         b_h, n_h = bpm.cpu().numpy(), nb.cpu().numpy()
         for k, i in enumerate(idx):
             res[i] = float(b_h[k]) if n_h[k] >= 4 else None
@@ -102,10 +103,7 @@ def ibis(eng: Engine, ys: Sequence[np.ndarray], start_bpms: Sequence[float], hop
     d = up.commit(eng.dev)
     core = eng.ibi_core(sig.buf, d["off"], d["len"], sig.length, d["start"],
                         torch.arange(len(ys), dtype=torch.int32, device=eng.dev), hop=hop, min_ibis=min_ibis)
-    vals = core["ibis"].cpu().numpy()
-    nibi = core["nibi"].cpu().numpy()
-    fb = core["fbase_h"]
-    return [vals[fb[i]:fb[i] + nibi[i]].copy() if nibi[i] > 0 else None for i in range(len(ys))]
+    return launch.ibi_lists(core["ibis"].cpu().numpy(), core["nibi"].cpu().numpy(), core["fbase_h"], 1)
 
 
 def chroma_means(eng: Engine, audios: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray, torch.Tensor]:
@@ -116,12 +114,7 @@ def chroma_means(eng: Engine, audios: Sequence[np.ndarray]) -> Tuple[np.ndarray,
     up.add("off", sig.off, np.int64)
     up.add("len", sig.length, np.int64)
     d = up.commit(eng.dev)
-    out = torch.empty(n * 12, dtype=torch.float32, device=eng.dev)
-    tun = torch.empty(n, dtype=torch.float32, device=eng.dev)
-    tot = int(sig.length.sum())
-    ws = eng.workspace("chroma", eng.ctx.lib.nc_chroma_workspace_bytes(eng.ctx.h, n, tot))
-    eng.call("nc_chroma_mean", sig.buf.data_ptr(), d["off"].data_ptr(), d["len"].data_ptr(), n, tot,
-             int(sig.length.max()), out.data_ptr(), tun.data_ptr(), None, None, ws.data_ptr(), ws.numel(), eng.stream())
+    out, tun, _ = launch.chroma_mean(eng, sig.buf, d["off"], d["len"], n, int(sig.length.sum()), int(sig.length.max()))
     return out.cpu().numpy().reshape(n, 12), tun.cpu().numpy(), out
 
 
@@ -225,7 +218,6 @@ def poly_plan(up: int, down: int, max_in: int):
     """scipy.signal.resample_poly's filter and offsets for ratio up/down (reduced), sized for
     inputs up to max_in samples: (up, down, h padded to a multiple of up (f64), pre_remove).
     Trailing zero taps beyond what a shorter input needs leave every sum unchanged."""
-    import math
     from scipy.signal import firwin
     g = math.gcd(int(up), int(down))
     up, down = int(up) // g, int(down) // g
@@ -256,15 +248,13 @@ def resample_poly(eng: Engine, arrays: Sequence[np.ndarray], up: int, down: int)
     if int(up) == int(down):
         return [a.copy() for a in arrays]
     out = resample_poly_device(eng, eng.upload_signals(arrays), up, down)
-    hy = out.buf.cpu().numpy()
-    return [hy[o:o + n].copy() for o, n in zip(out.off, out.length)]
+    return _read_back(out.buf, out.off, out.length)
 
 
 def resample_poly_device(eng: Engine, sig, up: int, down: int):
     """``resample_poly`` of signals already in HBM (``DeviceSignals``), the result left there
     (``DeviceSignals``, files back to back): the same launch, no host round trip and no
     synchronisation.  A 1:1 ratio returns ``sig`` itself."""
-    from .engine import DeviceSignals
     n = sig.n_files
     lens = np.asarray(sig.length, np.int64)
     if n == 0 or int(up) == int(down):
@@ -298,8 +288,6 @@ def flac_index(data, name: str = "FLAC data"):
     channel), md5 (STREAMINFO's 16 bytes).  The table's columns: byte start, byte end, first
     sample, block size, channel assignment, bits per sample, header bytes, 0.  ValueError
     (named after ``name``) for anything that is not a stream the decoder takes."""
-    import ctypes as C
-    from . import _native
     lib = _native.load()
     buf = np.frombuffer(bytes(data) or b"\0", np.uint8)
     n_bytes = len(data)
@@ -333,7 +321,6 @@ def flac_decode_device(eng: Engine, blobs: Sequence[bytes], *, names: Optional[S
     is not 0 raises ValueError naming the file, the frame and the reason (this reads the
     status words back: the one synchronisation).  ``verify_md5`` also downloads the samples
     and compares their MD5 with STREAMINFO's (skipped when that is all zeros)."""
-    from .engine import DeviceSignals
     names = [f"FLAC stream {i}" for i in range(len(blobs))] if names is None else [str(n) for n in names]
     infos, tables, chunks = [], [], []
     files = np.zeros((max(1, len(blobs)), 8), np.int64)
@@ -415,14 +402,9 @@ def flac_decode(eng: Engine, blobs: Sequence[bytes], **kw) -> List[Tuple[np.ndar
 
 
 # ------------------------------------------------------------------ speed render (speed.hip)
-from .engine import _ALIGN  # noqa: E402  (upload_signals' 64-sample file alignment)
-
-
 def speed_plan(factor: float, lengths: Sequence[int]) -> Tuple[int, np.ndarray]:
     """(P, n_out[file]) of a speed render: P = round(factor 1e6), n_out = ceil(n 1e6 / P), from
     the library's own ``nc_speed_out_len`` (the formula the kernel uses).  Needs no device."""
-    import ctypes as C
-    from . import _native
     lib = _native.load()
     n_in = np.ascontiguousarray(lengths, np.int64).reshape(-1)
     n_out = np.zeros(len(n_in), np.int64)
@@ -437,19 +419,16 @@ def speed_render_device(eng: Engine, src, factor: float):
     faster (the renderer's definition: DESIGN.md, include/ncgpu.h R2), one launch, the result
     left in HBM: (DeviceSignals of the renders, device float32 peak[file] = max |y|, P).  No
     host synchronisation."""
-    from .engine import DeviceSignals
-    sig = src if isinstance(src, DeviceSignals) else eng.upload_signals(list(src))
+    sig = _signals(eng, src, f32=False)
     n = sig.n_files
     P, n_out = speed_plan(factor, sig.length)
-    pad = (n_out + _ALIGN - 1) // _ALIGN * _ALIGN
-    o_off = np.zeros(n, np.int64)
-    o_off[1:] = np.cumsum(pad)[:-1]
+    o_off, total = _packed(n_out)
     up = _Upload()
     up.add("in_off", sig.off, np.int64)
     up.add("in_len", sig.length, np.int64)
     up.add("out_off", o_off, np.int64)
     d = up.commit(eng.dev)
-    y = torch.zeros(max(_ALIGN, int(pad.sum())), dtype=torch.float32, device=eng.dev)
+    y = torch.zeros(max(_ALIGN, total), dtype=torch.float32, device=eng.dev)
     peak = torch.empty(max(1, n), dtype=torch.float32, device=eng.dev)
     if n:
         eng.call("nc_speed_render", sig.buf.data_ptr(), d["in_off"].data_ptr(), d["in_len"].data_ptr(), n, P,
@@ -460,8 +439,7 @@ def speed_render_device(eng: Engine, src, factor: float):
 def speed_render(eng: Engine, arrays: Sequence[np.ndarray], factor: float) -> Tuple[List[np.ndarray], np.ndarray]:
     """(renders, peaks): each array played ``factor`` times faster, and max |y| of each."""
     out, peak, _ = speed_render_device(eng, [np.asarray(a, np.float32) for a in arrays], factor)
-    hy = out.buf.cpu().numpy()
-    return [hy[o:o + n].copy() for o, n in zip(out.off, out.length)], peak.cpu().numpy()
+    return _read_back(out.buf, out.off, out.length), peak.cpu().numpy()
 
 
 def f32_to_pcm16_device(eng: Engine, sig, interleave: bool = False):
@@ -475,10 +453,7 @@ def f32_to_pcm16_device(eng: Engine, sig, interleave: bool = False):
             raise ValueError("interleaved channels must be equally long")
         o_off, stride, total = np.arange(n, dtype=np.int64), max(1, n), int(lens.sum())
     else:
-        pad = (lens + _ALIGN - 1) // _ALIGN * _ALIGN
-        o_off = np.zeros(n, np.int64)
-        o_off[1:] = np.cumsum(pad)[:-1]
-        stride, total = 1, int(pad.sum())
+        stride, (o_off, total) = 1, _packed(lens)
     up = _Upload()
     up.add("in_off", sig.off, np.int64)
     up.add("in_len", lens, np.int64)
@@ -496,8 +471,7 @@ def f32_to_pcm16(eng: Engine, arrays: Sequence[np.ndarray]) -> Tuple[List[np.nda
     """(int16 arrays, clamped-sample counts) of float32 arrays (``nc_f32_to_pcm16``)."""
     sig = eng.upload_signals([np.asarray(a, np.float32) for a in arrays])
     q, off, clipped = f32_to_pcm16_device(eng, sig)
-    hq = q.cpu().numpy()
-    return [hq[o:o + n].copy() for o, n in zip(off, sig.length)], clipped.cpu().numpy()
+    return _read_back(q, off, sig.length), clipped.cpu().numpy()
 
 
 # ------------------------------------------------------------------ true-peak limiter (limiter.hip)
@@ -510,8 +484,7 @@ def limiter_windows(sr: int, attack_ms: float = 5.0, release_ms: float = 50.0) -
 def _limiter_files(eng: Engine, src, channels):
     """(DeviceSignals, first[file + 1], host lengths) of ``src`` grouped into files of
     ``channels`` consecutive signals (an int for every file, or one count per file)."""
-    from .engine import DeviceSignals
-    sig = src if isinstance(src, DeviceSignals) else eng.upload_signals([np.asarray(a, np.float32) for a in src])
+    sig = _signals(eng, src)
     n_sig = sig.n_files
     if isinstance(channels, (int, np.integer)):
         if int(channels) < 1 or n_sig % int(channels):
@@ -552,8 +525,6 @@ def true_peak_limit_device(eng: Engine, src, channels=1, limit_db: float = -0.1,
     (``limiter_windows``).  Returns (DeviceSignals of the limited signals — ``src``'s own buffer
     when ``in_place`` —, device float32 true peak in [file], device float32 sample peak out
     [file], device int32 limited frames [file]).  No host synchronisation."""
-    from . import _native
-    from .engine import DeviceSignals
     sig, first, lens = _limiter_files(eng, src, channels)
     n = len(first) - 1
     frames = np.ascontiguousarray(lens[first[:-1]], np.int64) if n else np.zeros(0, np.int64)
@@ -589,7 +560,6 @@ MAX_SEMITONES = 12.0
 def pitch_p(semitones: float) -> int:
     """P = round(2^(S / 12) 10^6) of a shift by S semitones, S first rounded to the six decimals
     the reference hands to rubberband (``--pitch {S:+.6f}``, workflow.py:129-130); |S| <= 12."""
-    import math
     s = float(semitones)
     if not math.isfinite(s) or not abs(round(s, 6)) <= MAX_SEMITONES:
         raise ValueError(f"pitch shift {semitones!r} outside [-{MAX_SEMITONES:g}, {MAX_SEMITONES:g}] semitones")
@@ -602,8 +572,6 @@ class PvPlan:
     ``ws_off`` [6] (mag, V, Phi, frame buffer, empty, scan) and ``ws_bytes``."""
 
     def __init__(self, P: int, lengths: Sequence[int]):
-        import ctypes as C
-        from . import _native
         lib = _native.load()
         n_in = np.ascontiguousarray(lengths, np.int64).reshape(-1)
         n = len(n_in)
@@ -620,15 +588,10 @@ class PvPlan:
         self.max_ns = int(self.ns.max()) if n else 0
 
 
-def _pv_signals(eng: Engine, src):
-    from .engine import DeviceSignals
-    return src if isinstance(src, DeviceSignals) else eng.upload_signals([np.asarray(a, np.float32) for a in src])
-
-
 def pv_analyze_device(eng: Engine, src, P: int):
     """Stage 1 alone (``nc_pv_analyze``): (mag [frames, 1025] f32, V [frames, 1025, 2] f32,
     empty [frames] uint8, PvPlan), all on the device."""
-    sig = _pv_signals(eng, src)
+    sig = _signals(eng, src)
     plan = PvPlan(P, sig.length)
     T = max(1, plan.total_frames)
     up = _Upload()
@@ -648,8 +611,6 @@ def pv_analyze_device(eng: Engine, src, P: int):
 def pv_scan_device(eng: Engine, v: torch.Tensor, empty: torch.Tensor, frame_base: Sequence[int]) -> torch.Tensor:
     """Stage 2 alone (``nc_pv_scan``): Phi [frames, 1025, 2] f32 from V and the empty flags of
     files whose frames start at ``frame_base`` [files + 1]."""
-    from . import _native
-    from .engine import h2d
     fb = np.ascontiguousarray(frame_base, np.int64).reshape(-1)
     n, total = len(fb) - 1, int(fb[-1])
     v = v.contiguous()
@@ -659,7 +620,7 @@ def pv_scan_device(eng: Engine, v: torch.Tensor, empty: torch.Tensor, frame_base
     phi = torch.empty_like(v)
     if total == 0:
         return phi
-    ws =eng.workspace("pv_scan", int(_native.load().nc_pv_scan_ws_bytes(total, n)))
+    ws = eng.workspace("pv_scan", int(_native.load().nc_pv_scan_ws_bytes(total, n)))
     d = h2d(fb, np.int64, eng.dev)
     eng.call("nc_pv_scan", v.data_ptr(), empty.data_ptr(), d.data_ptr(), n, total, int(np.diff(fb).max()),
              phi.data_ptr(), ws.data_ptr(), ws.numel(), eng.stream())
@@ -669,21 +630,18 @@ def pv_scan_device(eng: Engine, v: torch.Tensor, empty: torch.Tensor, frame_base
 def pv_synth_device(eng: Engine, mag: torch.Tensor, phi: torch.Tensor, lengths: Sequence[int], P: int):
     """Stage 3 alone (``nc_pv_synth``): (DeviceSignals of the stretched signals, device peak[file])
     from mag / Phi rows laid out by ``PvPlan(P, lengths)``."""
-    from .engine import DeviceSignals
     plan = PvPlan(P, lengths)
     mag, phi = mag.contiguous(), phi.contiguous()
     if tuple(mag.shape) != (plan.total_frames, PV_BINS) or tuple(phi.shape) != (plan.total_frames, PV_BINS, 2):
         raise ValueError("mag / Phi do not match the plan of these lengths")
     n = plan.n_files
-    pad = (plan.ns + _ALIGN - 1) // _ALIGN * _ALIGN
-    o_off = np.zeros(n, np.int64)
-    o_off[1:] = np.cumsum(pad)[:-1]
+    o_off, total = _packed(plan.ns)
     up = _Upload()
     up.add("len", np.asarray(lengths, np.int64), np.int64)
     up.add("fb", plan.frame_base, np.int64)
     up.add("out_off", o_off, np.int64)
     d = up.commit(eng.dev)
-    s = torch.zeros(max(_ALIGN, int(pad.sum())), dtype=torch.float32, device=eng.dev)
+    s = torch.zeros(max(_ALIGN, total), dtype=torch.float32, device=eng.dev)
     peak = torch.empty(max(1, n), dtype=torch.float32, device=eng.dev)
     fbytes = plan.total_frames * PV_N * 4
     frames = eng.workspace("pv_frames", fbytes)
@@ -699,20 +657,17 @@ def pv_stretch_device(eng: Engine, src, P: int):
     P / 10^6 with its pitch kept (the phase vocoder of DESIGN.md §4 "Pitch shift";
     ``nc_pv_stretch``, six launches), the result left in HBM: (DeviceSignals of the stretched
     signals, device float32 peak[file] = max |s|, PvPlan).  No host synchronisation."""
-    from .engine import DeviceSignals
-    sig = _pv_signals(eng, src)
+    sig = _signals(eng, src)
     plan = PvPlan(P, sig.length)
     n = plan.n_files
-    pad = (plan.ns + _ALIGN - 1) // _ALIGN * _ALIGN
-    o_off = np.zeros(n, np.int64)
-    o_off[1:] = np.cumsum(pad)[:-1]
+    o_off, total = _packed(plan.ns)
     up = _Upload()
     up.add("off", sig.off, np.int64)
     up.add("len", sig.length, np.int64)
     up.add("fb", plan.frame_base, np.int64)
     up.add("out_off", o_off, np.int64)
     d = up.commit(eng.dev)
-    s = torch.zeros(max(_ALIGN, int(pad.sum())), dtype=torch.float32, device=eng.dev)
+    s = torch.zeros(max(_ALIGN, total), dtype=torch.float32, device=eng.dev)
     peak = torch.empty(max(1, n), dtype=torch.float32, device=eng.dev)
     if n:
         ws = eng.workspace("pvoc", plan.ws_bytes)
@@ -729,8 +684,7 @@ def pitch_shift_device(eng: Engine, src, semitones: float):
     Returns (DeviceSignals of length n per file, device float32 peak[file] of the render, P).
     The peak is that of the whole render, ceil(Ns 10^6 / P) >= n samples.  No host
     synchronisation."""
-    from .engine import DeviceSignals
-    sig = _pv_signals(eng, src)
+    sig = _signals(eng, src)
     P = pitch_p(semitones)
     stretched, _, _ = pv_stretch_device(eng, sig, P)
     out, peak, _ = speed_render_device(eng, stretched, P / PV_Q)
@@ -740,5 +694,4 @@ def pitch_shift_device(eng: Engine, src, semitones: float):
 def pitch_shift(eng: Engine, arrays: Sequence[np.ndarray], semitones: float) -> List[np.ndarray]:
     """Each array shifted by ``semitones`` (float32, the input's length)."""
     out, _, _ = pitch_shift_device(eng, [np.asarray(a, np.float32) for a in arrays], semitones)
-    hy = out.buf.cpu().numpy()
-    return [hy[o:o + n].copy() for o, n in zip(out.off, out.length)]
+    return _read_back(out.buf, out.off, out.length)

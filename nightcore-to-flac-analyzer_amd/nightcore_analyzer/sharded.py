@@ -78,6 +78,7 @@ import torch
 import torch.distributed as dist
 
 from . import consensus as C
+from . import launch
 from .distributed import shard_range
 from .engine import (CHUNK_SEC, HOP_LENGTH, IBI_HOP, MIN_BEATS, MIN_CHUNKS, REF_HZ, SR, AsmContext, DeviceSignals,
                      Engine, PairOutcome, Params, _HostViews, _Upload, plan_batch, window_files_by_offset)
@@ -782,22 +783,15 @@ class DeviceStages:
         if n == 0:
             self._win = None
             return np.zeros(0)
-        T = 1 + win_n // HOP_LENGTH
-        acw = int(int(8.0 * SR) // HOP_LENGTH)
         with torch.cuda.stream(self.stream):
             off = torch.from_numpy(np.ascontiguousarray(win_abs, np.int64)).to(eng.dev)
-            onset = torch.empty(n * T, dtype=torch.float32, device=eng.dev)
-            tg = torch.empty(n * acw, dtype=torch.float64, device=eng.dev)
             en = torch.empty(n, dtype=torch.float64, device=eng.dev)
-            ws = eng.workspace("sp_win", eng.ctx.lib.nc_window_stage_workspace_bytes(eng.ctx.h, n, win_n, HOP_LENGTH))
-            en_ptr = en.data_ptr()
             tb = self._blocks
             if tb is not None:          # energies from the trim's block sums, as in the engine's groups
                 wf_d = torch.from_numpy(window_files_by_offset(self.off, win_abs)).to(eng.dev)
-                tb.window_energies(off, wf_d, n, win_n, en_ptr)
-                en_ptr = None
-            eng.call("nc_window_stage", self.sig.buf.data_ptr(), off.data_ptr(), None, n, win_n, HOP_LENGTH,
-                     onset.data_ptr(), tg.data_ptr(), en_ptr, ws.data_ptr(), ws.numel(), eng.stream())
+                tb.window_energies(off, wf_d, n, win_n, en.data_ptr())
+            onset, tg, T, acw = launch.window_stage(eng, self.sig.buf, off, n, win_n, HOP_LENGTH, SR,
+                                                    energy=en if tb is None else None, ws_tag="sp_win")
             self._win = dict(onset=onset, tg=tg, T=T, acw=acw)
             return en.cpu().numpy()
 
@@ -818,17 +812,10 @@ class DeviceStages:
             up.add("sel", np.asarray(sel, np.int64), np.int64)
             d = up.commit(eng.dev)
             tg = w["tg"].view(-1, acw)[d["sel"]].contiguous()
-            res = torch.zeros(4 * n, dtype=torch.float64, device=eng.dev)
-            lag = torch.zeros(n, dtype=torch.int32, device=eng.dev)
-            nb = torch.zeros(n, dtype=torch.int32, device=eng.dev)
-            ws = eng.workspace("sp_beats", eng.ctx.lib.nc_tempo_beats_workspace_bytes(n * T))  # any window length
-            eng.call("nc_tempo_beats", w["onset"].data_ptr(), d["on_off"].data_ptr(), d["on_len"].data_ptr(), n, T,
-                     tg.data_ptr(), acw, d["start"].data_ptr(), None, None, HOP_LENGTH, 1, res[:n].data_ptr(),
-                     lag.data_ptr(), nb.data_ptr(), res[3 * n:].data_ptr(), None, n * T, ws.data_ptr(), ws.numel(),
-                     eng.stream())
-            res[n:2 * n] = nb.to(torch.float64)
-            res[2 * n:3 * n] = lag.to(torch.float64)
-            return res.cpu().numpy().reshape(4, n).T.copy()        # one read-back for the four fields
+            bpm, lag, nb, mg = launch.tempo_beats(eng, w["onset"], d["on_off"], d["on_len"], n, T, tg, acw, d["start"],
+                                                  HOP_LENGTH, total=n * T, ws_tag="sp_beats")  # any window length
+            res = torch.stack([bpm, nb.to(torch.float64), lag.to(torch.float64), mg])
+            return res.cpu().numpy().T.copy()                       # one read-back for the four fields
 
     def chunks(self, chunk_off: Sequence[int], chunk_len: Sequence[int]) -> np.ndarray:
         """Mean chroma of every chunk (files interleaved src, nc per chunk pair) and the
@@ -844,18 +831,10 @@ class DeviceStages:
             up.add("si", np.arange(0, n, 2), np.int32)
             up.add("ni", np.arange(1, n, 2), np.int32)
             d = up.commit(eng.dev)
-            chroma = torch.empty(n * 12, dtype=torch.float32, device=eng.dev)
-            tun = torch.empty(n, dtype=torch.float32, device=eng.dev)
-            lag = torch.empty(n // 2, dtype=torch.int32, device=eng.dev)
             tmg = torch.empty(n, dtype=torch.int32, device=eng.dev)
-            tot = int(np.sum(chunk_len))
-            ws = eng.workspace("sp_chroma", eng.ctx.lib.nc_chroma_workspace_bytes(eng.ctx.h, n, tot))
-            eng.call("nc_chroma_mean", self.sig.buf.data_ptr(), d["off"].data_ptr(), d["len"].data_ptr(), n, tot,
-                     int(max(chunk_len)), chroma.data_ptr(), tun.data_ptr(), None, tmg.data_ptr(), ws.data_ptr(), ws.numel(),
-                     eng.stream())
-            mg = torch.empty(n // 2, dtype=torch.float64, device=eng.dev)
-            eng.call("nc_chroma_lag_margin", chroma.data_ptr(), d["si"].data_ptr(), d["ni"].data_ptr(), n // 2,
-                     lag.data_ptr(), mg.data_ptr(), eng.stream())
+            chroma, tun, _ = launch.chroma_mean(eng, self.sig.buf, d["off"], d["len"], n, int(np.sum(chunk_len)),
+                                                int(max(chunk_len)), tmargin=tmg, ws_tag="sp_chroma")
+            lag, mg = launch.chroma_lag_margin(eng, chroma, d["si"], d["ni"], n // 2)
             rec = torch.cat([lag.to(torch.float64)[:, None], tun.to(torch.float64).view(-1, 2),
                              chroma.to(torch.float64).view(-1, 24), mg[:, None], tmg.to(torch.float64).view(-1, 2)],
                             dim=1)
@@ -882,9 +861,8 @@ class DeviceStages:
             d = up.commit(eng.dev)
             core = eng.ibi_core(self.sig.buf, d["off"], d["len"], np.asarray(f_len, np.int64), d["start"],
                                 torch.arange(n, dtype=torch.int32, device=eng.dev), ws_tag="sp_")
-            vals, nibi = core["ibis"].cpu().numpy(), core["nibi"].cpu().numpy()
-            fb = core["fbase_h"]
-            ibis = [vals[fb[i]:fb[i] + nibi[i]].copy() if nibi[i] >= 4 else None for i in range(n)]
+            nibi = core["nibi"].cpu().numpy()
+            ibis = launch.ibi_lists(core["ibis"].cpu().numpy(), nibi, core["fbase_h"], 4)
             return ibis, nibi, core["nbeats"].cpu().numpy(), core["lag"].cpu().numpy()
 
 
@@ -892,7 +870,7 @@ class DeviceStages:
     def ibi_mel(self, f_off, f_len, t0, t1) -> np.ndarray:
         """Mel dB rows for this rank's onset frames [t0, t1) of each file -> per-file max."""
         eng, n = self.eng, len(f_off)
-        T = 1 + np.asarray(f_len, np.int64) // IBI_HOP
+        T = launch.frames_of(np.asarray(f_len, np.int64), IBI_HOP)
         t0, t1 = np.asarray(t0, np.int64), np.asarray(t1, np.int64)
         rr = _ibi_mel_rows(T, t0, t1)
         rows = int((rr[:, 1] - rr[:, 0]).sum())
@@ -929,7 +907,7 @@ class DeviceStages:
         eng = self.eng
         T = np.array([len(o) for o in onsets], np.int64)
         n, total, mxf = len(T), int(T.sum()), int(T.max())
-        N = int(int(8.0 * SR) // IBI_HOP)
+        N = launch.tempogram_window(SR, IBI_HOP)
         ntb = -(-mxf // IBI_TILE)
         sel = [f * ntb + b for f in range(n) for b in range(int(b0[f]), int(b1[f]))]
         if not sel:
@@ -983,24 +961,11 @@ class DeviceStages:
             up.add("start", start_bpm, np.float64)
             up.add("pidx", np.arange(n), np.int32)
             d = up.commit(eng.dev)
-            bpm = torch.zeros(n, dtype=torch.float64, device=eng.dev)
-            lag = torch.zeros(n, dtype=torch.int32, device=eng.dev)
-            nb = torch.zeros(n, dtype=torch.int32, device=eng.dev)
-            mg = torch.zeros(n, dtype=torch.float64, device=eng.dev)
-            beats = torch.empty(max(1, total), dtype=torch.int32, device=eng.dev)
-            ws = eng.workspace("sp_ibi_beats", eng.ctx.lib.nc_tempo_beats_workspace_bytes(total))
-            eng.call("nc_tempo_beats", d["onset"].data_ptr(), d["fb"].data_ptr(), d["len"].data_ptr(), n, int(T.max()),
-                     d["tg"].data_ptr(), N, d["start"].data_ptr(), d["pidx"].data_ptr(), None, IBI_HOP, 1,
-                     bpm.data_ptr(), lag.data_ptr(), nb.data_ptr(), mg.data_ptr(), beats.data_ptr(), total,
-                     ws.data_ptr(), ws.numel(), eng.stream())
-            ibis = torch.empty(max(1, total), dtype=torch.float64, device=eng.dev)
-            nibi = torch.zeros(n, dtype=torch.int32, device=eng.dev)
-            eng.call("nc_ibi_from_beats", beats.data_ptr(), d["fb"].data_ptr(), nb.data_ptr(), n, IBI_HOP, 4,
-                     ibis.data_ptr(), nibi.data_ptr(), eng.stream())
-            vals, ni = ibis.cpu().numpy(), nibi.cpu().numpy()
-            fb = np.concatenate([[0], np.cumsum(T)])
-            out = [vals[fb[i]:fb[i] + ni[i]].copy() if ni[i] >= 4 else None for i in range(n)]
-            return out, ni, nb.cpu().numpy(), lag.cpu().numpy()
+            r = launch.beats_to_ibis(eng, d["onset"], d["fb"], d["len"], n, int(T.max()), d["tg"], N, d["start"],
+                                     d["pidx"], IBI_HOP, 4, total, "sp_ibi_beats")
+            ni = r["nibi"].cpu().numpy()
+            out = launch.ibi_lists(r["ibis"].cpu().numpy(), ni, np.concatenate([[0], np.cumsum(T)]), 4)
+            return out, ni, r["nbeats"].cpu().numpy(), r["lag"].cpu().numpy()
 
 
 # ------------------------------------------------------------------------------ orchestration
