@@ -677,6 +677,47 @@ int nc_flac_decode(nc_ctx* ctx, const uint8_t* data, int64_t data_bytes, const i
                    const int64_t* files, int n_files, int32_t* pcm, float* pcm_f32, int64_t pcm_len, float* mono,
                    int64_t mono_len, int* status, void* stream);
 
+/* -------------------------------------------------------------------------
+ * FLAC encode — what the reference's workflow gets from sox / rubberband / ffmpeg when
+ * they write `Song [Nightcore].flac` and its UPD / PS / ADJ versions.  Fixed block size
+ * streams, 1-8 channels, 4-24 bits, block 16 .. 16384 (a stream's last frame: 1 .. block);
+ * CONSTANT, VERBATIM, FIXED 0-4 and (level 1) LPC 1-8 subframes, Rice partitions of order
+ * 0-6 with the exact parameter search, the four stereo assignments; no wasted bits, no
+ * escape partitions.  The choice rule is integer-only at level 0 (DESIGN.md §4 "FLAC
+ * encode", restated in tests/flac_enc_ref.py); a level 1 frame is never longer than the
+ * level 0 frame.  The host writes "fLaC" and STREAMINFO (io.write_flac).
+ *
+ * nc_flac_encode: the frames of several streams in one launch, one wave per frame.
+ *     files:  device int64 [n_files][8] = in_off, channel stride, channels, bits per
+ *             sample, sample rate, total samples, 0, 0.  Channel c's sample i is
+ *             in[in_off + c stride + i].
+ *     frames: device int64 [n_frames][8] = file, first sample, block size, frame number,
+ *             slot offset (bytes into slots, a multiple of 4), 0, 0, 0.
+ *     Give either pcm_in (int32 samples inside the sample size) or f32_in with pcm_q:
+ *     q = clamp(rint(x 2^(bits-1)), -2^(bits-1), 2^(bits-1) - 1), round half to even
+ *     (nc_f32_to_pcm16's rule at 16 bits), is stored in pcm_q at the input's index and
+ *     clipped[frame] counts the clamped samples.  With pcm_in, pcm_q is nullable and
+ *     receives a copy.  in_len: the sample buffers' length.
+ *     A frame's slot holds 16 + ceil(channels (8 + block (bits + 1)) / 8) + 2 bytes
+ *     rounded up to 4 (all-VERBATIM with the header's bound), which no frame exceeds.
+ *     frame_bytes[frame] = the frame's length; records[frame][25] = assignment, then
+ *     per channel the subframe type (0 CONSTANT, 1 VERBATIM, 2 FIXED, 3 LPC), order and
+ *     partition order; status[frame] = 0 ok, 1 a table row that does not fit the
+ *     buffers or the limits above, 2 an int32 sample outside the sample size (nothing
+ *     is read or written through such a row; frame_bytes is 0).  No workspace, no host
+ *     synchronisation.
+ * nc_flac_pack: out[offsets[frame] .. + frame_bytes[frame]) = the frame's slot, for all
+ *     frames in one launch; offsets: device int64 [n_frames], the exclusive running sum
+ *     of frame_bytes.  out (4-byte aligned, out_bytes a multiple of 4) is zeroed first.
+ *     A frame whose row or offset does not fit the buffers is left out.
+ * ------------------------------------------------------------------------- */
+int nc_flac_encode(nc_ctx* ctx, const int32_t* pcm_in, const float* f32_in, int32_t* pcm_q, int64_t in_len,
+                   const int64_t* frames, int64_t n_frames, const int64_t* files, int n_files, int level,
+                   uint8_t* slots, int64_t slot_bytes, int* frame_bytes, int* records, int* clipped, int* status,
+                   void* stream);
+int nc_flac_pack(nc_ctx* ctx, const uint8_t* slots, int64_t slot_bytes, const int64_t* frames, int64_t n_frames,
+                 const int* frame_bytes, const int64_t* offsets, uint8_t* out, int64_t out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

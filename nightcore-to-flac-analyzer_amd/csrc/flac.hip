@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "nc_engine.h"
+#include "nc_flac_crc.h"
 
 namespace nc {
 namespace {
@@ -218,34 +219,6 @@ __device__ uint32_t parse_frame(Bits& b, Sub* sub, int* out0, int64_t stride, in
   return b.pos >> 3;
 }
 
-__device__ inline uint32_t gf_mulmod(uint32_t a, uint32_t m) {  // a m mod x^16 + 0x8005
-  uint32_t r = 0;
-  for (int i = 15; i >= 0; --i) {
-    r = ((r << 1) ^ ((r & 0x8000) ? 0x8005u : 0u)) & 0xffff;
-    if ((m >> i) & 1) r ^= a;
-  }
-  return r;
-}
-
-// CRC-16 (poly 0x8005, init 0) of p[0 .. n) by the whole wave; the result is valid in lane 0
-__device__ uint32_t wave_crc16(const uint8_t* p, uint32_t n, const uint16_t* tab, int lane) {
-  const uint32_t chunk = (n + 63) / 64;
-  const int64_t pad = (int64_t)chunk * 64 - n;  // leading zero bytes leave a CRC with init 0 unchanged
-  uint32_t crc = 0, xl = 1;                     // xl = x^(8 chunk)
-  for (uint32_t j = 0; j < chunk; ++j) {
-    const int64_t g = (int64_t)lane * chunk + j - pad;
-    const uint32_t byte = g >= 0 ? p[g] : 0;
-    crc = ((crc << 8) ^ tab[(crc >> 8) ^ byte]) & 0xffff;
-    xl = ((xl << 8) ^ tab[xl >> 8]) & 0xffff;
-  }
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t right = __shfl_down(crc, d, 64);
-    crc = gf_mulmod(crc, xl) ^ right;
-    xl = gf_mulmod(xl, xl);
-  }
-  return crc;
-}
-
 // phase D for predictor orders up to M (history and coefficients in registers)
 template <int M>
 __device__ void restore(const Sub* sub, int (*tile)[64], int* out0, int64_t stride, int nch, int block, int lane) {
@@ -328,11 +301,7 @@ __global__ __launch_bounds__(64) void flac_frame_kernel(const uint8_t* __restric
   const int block = (int)block64, assign = (int)assign64, bps = (int)bps64;
   int* out0 = pcm + out_off + first;  // channel c's slots: out0[c stride + i], i < block
 
-  for (int i = lane; i < 256; i += 64) {
-    uint32_t c = (uint32_t)i << 8;
-    for (int k = 0; k < 8; ++k) c = ((c << 1) ^ ((c & 0x8000) ? 0x8005u : 0u)) & 0xffff;
-    crc_tab[i] = (uint16_t)c;
-  }
+  crc16_fill_table(crc_tab, lane);
   if (lane == 0) {
     Bits b;
     b.words = reinterpret_cast<const uint32_t*>(data);
@@ -351,7 +320,8 @@ __global__ __launch_bounds__(64) void flac_frame_kernel(const uint8_t* __restric
     return;
   }
   const uint32_t foot = s_foot;  // foot + 2 <= end - start
-  const uint32_t crc = wave_crc16(data + start, foot, crc_tab, lane);
+  const uint8_t* fbytes = data + start;
+  const uint32_t crc = wave_crc16([fbytes](int64_t g) { return (uint32_t)fbytes[g]; }, foot, crc_tab, lane);
   if (lane == 0) {
     const uint32_t stored = ((uint32_t)data[start + foot] << 8) | data[start + foot + 1];
     status[fr] = crc == stored ? FL_OK : FL_CRC;

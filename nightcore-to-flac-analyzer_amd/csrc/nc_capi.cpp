@@ -138,6 +138,11 @@ int launch_window_energy(const float* sig, const int64_t* off, int n, int win_le
 int launch_flac_decode(const uint8_t* data, int64_t data_bytes, const int64_t* frames, int64_t n_frames,
                        const int64_t* files, int n_files, int* pcm, float* f32, int64_t pcm_len, float* mono,
                        int64_t mono_len, int* status, hipStream_t st);
+int launch_flac_encode(const int* pcm_in, const float* f32_in, int* pcm_q, int64_t in_len, const int64_t* frames,
+                       int64_t n_frames, const int64_t* files, int n_files, int level, uint8_t* slots,
+                       int64_t slot_bytes, int* frame_bytes, int* records, int* clipped, int* status, hipStream_t st);
+int launch_flac_pack(const uint8_t* slots, int64_t slot_bytes, const int64_t* frames, int64_t n_frames,
+                     const int* frame_bytes, const int64_t* offsets, uint8_t* out, int64_t out_bytes, hipStream_t st);
 
 }  // namespace nc
 
@@ -622,6 +627,24 @@ int nc_flac_decode(nc_ctx* ctx, const uint8_t* data, int64_t data_bytes, const i
   nc::MarkSpan ms_(ctx->c, "flac_decode", (hipStream_t)stream);
   return nc::launch_flac_decode(data, data_bytes, frames, n_frames, files, n_files, pcm, pcm_f32, pcm_len, mono,
                                 mono_len, status, (hipStream_t)stream);
+}
+
+int nc_flac_encode(nc_ctx* ctx, const int32_t* pcm_in, const float* f32_in, int32_t* pcm_q, int64_t in_len,
+                   const int64_t* frames, int64_t n_frames, const int64_t* files, int n_files, int level,
+                   uint8_t* slots, int64_t slot_bytes, int* frame_bytes, int* records, int* clipped, int* status,
+                   void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_flac_encode(pcm_in, f32_in, pcm_q, in_len, frames, n_frames, files, n_files, level, slots,
+                                slot_bytes, frame_bytes, records, clipped, status, (hipStream_t)stream);
+}
+
+int nc_flac_pack(nc_ctx* ctx, const uint8_t* slots, int64_t slot_bytes, const int64_t* frames, int64_t n_frames,
+                 const int* frame_bytes, const int64_t* offsets, uint8_t* out, int64_t out_bytes, void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_flac_pack(slots, slot_bytes, frames, n_frames, frame_bytes, offsets, out, out_bytes,
+                              (hipStream_t)stream);
 }
 
 int nc_speed_out_len(double factor, const int64_t* n_in, int n_files, int64_t* p_out, int64_t* n_out) {

@@ -93,6 +93,8 @@ SIGNATURES = {
     "nc_pv_stretch": (I32, [P, P, P, P, P, I32, I64, I64, I64, I64, P, P, P, P, P, SZ, P]),
     "nc_flac_index": (I32, [P, I64, P, P, P, I64, C.POINTER(I64)]),
     "nc_flac_decode": (I32, [P, P, I64, P, I64, P, I32, P, P, I64, P, I64, P, P]),
+    "nc_flac_encode": (I32, [P, P, P, P, I64, P, I64, P, I32, I32, P, I64, P, P, P, P, P]),
+    "nc_flac_pack": (I32, [P, P, I64, P, I64, P, P, P, I64, P]),
 }
 
 

@@ -37,18 +37,19 @@ def _build_parser() -> argparse.ArgumentParser:
     p.add_argument("--auto-align", action="store_true", default=False,
                    help="Attempt automatic intro-offset detection (RMS envelope correlation)")
     p.add_argument("--quiet", "-q", action="store_true", help="Suppress progress output")
-    p.add_argument("--render-hqnc", metavar="OUT.wav", default=None,
+    p.add_argument("--render-hqnc", metavar="OUT.{wav,flac}", default=None,
                    help="After the analysis, render the source sped up by the detected factor (IBI ratio, "
-                        "else tempo ratio) to this WAV file on the GPU")
+                        "else tempo ratio) to this file on the GPU: WAV, or FLAC (encoded on the GPU) when "
+                        "the name ends in .flac")
     p.add_argument("--refine", action="store_true",
                    help="With --render-hqnc: re-analyse the render against the nightcore and correct the "
                         "factor until the residual is inside tolerance before writing the file")
     p.add_argument("--limit", type=float, nargs="?", const=-0.1, default=None, metavar="DB",
                    help="With --render-hqnc: limit the render to this true-peak ceiling in dBFS on the GPU "
                         "before it is written (-0.1 when no value is given); applies to --pitch-correct too")
-    p.add_argument("--pitch-correct", metavar="OUT.wav", default=None,
+    p.add_argument("--pitch-correct", metavar="OUT.{wav,flac}", default=None,
                    help="After the analysis, write the source shifted in pitch by --semitones (duration kept) "
-                        "to this WAV file on the GPU")
+                        "to this file on the GPU: WAV, or FLAC when the name ends in .flac")
     p.add_argument("--semitones", type=float, default=None, metavar="S",
                    help="With --pitch-correct: the shift in semitones (-12 .. 12)")
     return p

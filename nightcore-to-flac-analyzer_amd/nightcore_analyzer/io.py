@@ -19,6 +19,9 @@
 * ``read_wav_channels`` / ``write_wav`` (no counterpart in the reference's io.py, which leaves
   this to soundfile and sox): the channel-preserving WAV read and the WAV writer behind
   ``render.speed_file`` and ``loudness``; ``DeviceAudio`` is a signal that is already in HBM.
+* ``write_flac`` / ``write_flac_device`` / ``write_audio``: the FLAC writer (frames encoded on the
+  GPU by ``nc_flac_encode``, one wave per frame; ``fLaC`` and STREAMINFO added on the host), its
+  form for a signal already in HBM, and the dispatch on the suffix.
 """
 from __future__ import annotations
 
@@ -275,7 +278,8 @@ def write_wav(path, data, sr: int, sample_format: str = "float32") -> None:
     """Write ``data`` ([channels, frames] or [frames]) as a RIFF/WAVE file of 16-bit PCM
     ("pcm16") or IEEE float32 ("float32").  int16 data is written as stored (the renderer
     quantises on the device, ``nc_f32_to_pcm16``); float data going to "pcm16" is quantised
-    here by the same rule (``quantize_pcm16``).  File encode stays on the CPU; the output is WAV."""
+    here by the same rule (``quantize_pcm16``).  The RIFF container is assembled on the CPU;
+    ``write_flac`` is the compressed sibling and ``write_audio`` picks between them by suffix."""
     a = np.asarray(data)
     if a.ndim == 1:
         a = a[None, :]
@@ -298,6 +302,86 @@ def write_wav(path, data, sr: int, sample_format: str = "float32") -> None:
            + (8 * width).to_bytes(2, "little"))
     head = b"RIFF" + (36 + len(body)).to_bytes(4, "little") + b"WAVE" + b"fmt " + (16).to_bytes(4, "little") + fmt
     Path(path).write_bytes(head + b"data" + len(body).to_bytes(4, "little") + body)
+
+
+def flac_stream_header(sr: int, channels: int, bits: int, total: int, block: int, min_frame: int, max_frame: int,
+                       md5: bytes = bytes(16)) -> bytes:
+    """``fLaC`` and one STREAMINFO block, marked last: min_block = max_block = ``block``."""
+    packed = (int(sr) << 44) | ((channels - 1) << 41) | ((bits - 1) << 36) | int(total)
+    si = (int(block).to_bytes(2, "big") * 2 + int(min_frame).to_bytes(3, "big") + int(max_frame).to_bytes(3, "big")
+          + packed.to_bytes(8, "big") + bytes(md5))
+    return b"fLaC" + bytes([0x80]) + len(si).to_bytes(3, "big") + si
+
+
+def write_flac_device(path, eng, sig, sr: int, bits: int = 16, *, block: int = 4096, level: int = 1,
+                      md5: bool = True) -> dict:
+    """Write the equally long channels ``sig`` (a ``DeviceSignals`` resident in HBM, float32 or
+    int32) as one FLAC file, encoded on the device (``ops.flac_encode_device``); returns the
+    stream's info dict.  ``md5``: STREAMINFO's MD5 is hashed on the host from a download of the
+    quantised samples; without it the field is sixteen zero bytes and no sample is downloaded."""
+    import hashlib
+    import torch
+    from .ops import flac_encode_device
+    (blob,), (info,) = flac_encode_device(eng, sig, [sig.n_files], bits, sr, block, level, names=[str(path)])
+    digest = bytes(16)
+    if md5:
+        width = (bits + 7) // 8        # interleaved little-endian samples of `width` bytes, cut on the device
+        inter = info["pcm"].t().clone(memory_format=torch.contiguous_format).reshape(-1)
+        inter = inter.view(torch.uint8).view(-1, 4)[:, :width].contiguous()
+        digest = hashlib.md5(inter.cpu().numpy().tobytes()).digest()
+    head = flac_stream_header(sr, info["channels"], bits, info["total"], block, info["min_frame"], info["max_frame"],
+                              digest)
+    Path(path).write_bytes(head + blob)
+    return info
+
+
+def write_flac(path, data, sr: int, bits: int = 16, *, block: int = 4096, level: int = 1, md5: bool = True) -> dict:
+    """Write ``data`` ([channels, frames] or [frames], 1-8 channels) as a FLAC file of ``bits``
+    (4-24) per sample, encoded on the GPU.  Float data is quantised on the device by
+    clamp(rint(x 2^(bits-1))) (round half to even; ``quantize_pcm16`` at 16 bits); integer data
+    is taken as the samples themselves and must fit ``bits``.  ``block`` (16 .. 16384) is the
+    fixed block size, ``level`` 0 or 1 the encoder's effort.  Returns the stream's info dict
+    (``clipped``: samples the quantiser clamped)."""
+    import torch
+    from .engine import _ALIGN, DeviceSignals, get_engine
+    a = np.asarray(data)
+    if a.ndim == 1:
+        a = a[None, :]
+    if a.ndim != 2 or not 1 <= a.shape[0] <= 8:
+        raise ValueError("write_flac: data must be [frames] or [channels, frames] with 1 .. 8 channels")
+    if not 4 <= int(bits) <= 24:
+        raise ValueError(f"write_flac: {bits} bits per sample outside 4 .. 24")
+    if not 16 <= int(block) <= 16384:
+        raise ValueError(f"write_flac: block size {block} outside 16 .. 16384")
+    if not 0 < int(sr) < 1 << 20:
+        raise ValueError(f"write_flac: sample rate {sr} outside 1 .. 2^20 - 1")
+    integer = a.dtype.kind in "iu"
+    if integer and a.size and (a.min() < -(1 << (bits - 1)) or a.max() >= 1 << (bits - 1)):
+        raise ValueError(f"write_flac: integer samples outside {bits} bits")
+    ch, n = a.shape
+    stride = (n + _ALIGN - 1) // _ALIGN * _ALIGN
+    host = torch.zeros(max(_ALIGN, ch * stride), dtype=torch.int32 if integer else torch.float32, pin_memory=True)
+    host.numpy()[:ch * stride].reshape(ch, stride)[:, :n] = a
+    eng = get_engine()
+    sig = DeviceSignals(host.to(eng.dev, non_blocking=True), np.arange(ch, dtype=np.int64) * stride,
+                        np.full(ch, n, np.int64))
+    return write_flac_device(path, eng, sig, int(sr), int(bits), block=int(block), level=int(level), md5=md5)
+
+
+def write_audio(path, data, sr: int, sample_format: str = "float32", **flac_kw) -> None:
+    """``write_flac`` for a ``.flac`` path, else ``write_wav``.  A FLAC file gets 16 bits per
+    sample for "pcm<b>" with b <= 16 and 24 bits for every other format (``flac_bits``)."""
+    if Path(path).suffix.lower() == ".flac":
+        write_flac(path, data, sr, flac_bits(sample_format), **flac_kw)
+    else:
+        write_wav(path, data, sr, sample_format)
+
+
+def flac_bits(sample_format: str) -> int:
+    """Bits per sample of the FLAC file written for a source of ``sample_format``: 16 for
+    "pcm<b>" with b <= 16, else 24."""
+    fmt = str(sample_format)
+    return 16 if fmt.startswith("pcm") and fmt[3:].isdigit() and int(fmt[3:]) <= 16 else 24
 
 
 def load_audio(path: str, sr: Optional[int] = SAMPLE_RATE, *, keep_pcm16: bool = False,

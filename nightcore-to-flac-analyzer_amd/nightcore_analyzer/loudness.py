@@ -14,7 +14,8 @@
 * ``detect_true_peak``: the inter-sample companion of ``detect_peak`` (the limiter's own 4x
   estimate, ``nc_true_peak``).
 
-File decode and encode stay on the CPU (io.read_wav_channels / io.write_wav); a render's own
+The source is a WAV file (io.read_wav_channels); the result is written as WAV (io.write_wav) or,
+to a ``.flac`` name, as FLAC encoded on the device (io.write_flac); a render's own
 peak and clamp count come from the device (render.speed_file's RenderInfo).
 """
 from __future__ import annotations
@@ -25,7 +26,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .io import read_wav_channels, write_wav
+from .io import flac_bits, read_wav_channels, write_flac, write_flac_device, write_wav
 
 
 def _channels(path) -> tuple[np.ndarray, int, str]:
@@ -54,11 +55,15 @@ def make_adj_path(src, version: int) -> Path:
 
 
 def apply_gain_reduction(src, dst, gain_db: float) -> None:
-    """Write ``src`` scaled by ``gain_db`` decibels (negative reduces the level) to ``dst``."""
+    """Write ``src`` scaled by ``gain_db`` decibels (negative reduces the level) to ``dst`` (WAV,
+    or FLAC for a ``.flac`` name)."""
     data, sr, fmt = _channels(src)
-    if Path(dst).suffix.lower() != ".wav":
-        raise NotImplementedError("only WAV output is written")
+    if Path(dst).suffix.lower() not in (".wav", ".flac"):
+        raise NotImplementedError("only WAV and FLAC output is written")
     scaled = (data.astype(np.float64) * 10.0 ** (float(gain_db) / 20.0)).astype(np.float32)
+    if Path(dst).suffix.lower() == ".flac":
+        write_flac(dst, scaled, sr, flac_bits(fmt))
+        return
     write_wav(dst, scaled, sr, "pcm16" if fmt == "pcm16" else "float32")
 
 
@@ -95,25 +100,29 @@ def apply_true_peak_limiter(src, dst, limit_db: float = -0.1, *, attack_ms: floa
                             release_ms: float = 50.0) -> LimitInfo:
     """Write ``src`` limited to a true-peak ceiling of ``limit_db`` dBFS to ``dst`` (WAV, the
     source's sample format: 16-bit PCM stays 16-bit PCM, quantised on the device; anything else
-    becomes float32).  Attenuates only around the over-peaks; the channels share one gain."""
+    becomes float32; or FLAC for a ``.flac`` name, encoded on the device: 16 bits for a source of
+    at most 16 bits, else 24).  Attenuates only around the over-peaks; the channels share one gain."""
     from .engine import get_engine
     from .ops import f32_to_pcm16_device, limiter_windows, true_peak_limit_device
     if not float(limit_db) <= 0.0:
         raise ValueError(f"limiter ceiling {limit_db!r} dBFS is above full scale")
     data, sr, fmt = _channels(src)
-    if Path(dst).suffix.lower() != ".wav":
-        raise NotImplementedError("only WAV output is written")
+    if Path(dst).suffix.lower() not in (".wav", ".flac"):
+        raise NotImplementedError("only WAV and FLAC output is written")
     ch, n = data.shape
     wa, wr = limiter_windows(sr, attack_ms, release_ms)
     eng = get_engine()
     out, tp_d, pk_d, lim_d = true_peak_limit_device(eng, list(data), ch, float(limit_db), wa, wr, in_place=True)
-    if fmt == "pcm16":
+    if Path(dst).suffix.lower() == ".flac":      # encoded from the resident result: no float download
+        from .engine import DeviceSignals
+        write_flac_device(dst, eng, DeviceSignals(out.buf, np.asarray(out.off[:ch], np.int64), np.full(ch, n, np.int64)),
+                          sr, flac_bits(fmt))
+    elif fmt == "pcm16":
         q, _, _ = f32_to_pcm16_device(eng, out, interleave=True)
-        frames, out_fmt = q[:ch * n].cpu().numpy().reshape(n, ch).T, "pcm16"
+        write_wav(dst, q[:ch * n].cpu().numpy().reshape(n, ch).T, sr, "pcm16")
     else:
         hy = out.buf.cpu().numpy()
-        frames, out_fmt = np.stack([hy[o:o + n] for o in out.off]), "float32"
-    write_wav(dst, frames, sr, out_fmt)
+        write_wav(dst, np.stack([hy[o:o + n] for o in out.off]), sr, "float32")
     print(f"  Created: {dst}")
     tp = float(tp_d[0].item())
     return LimitInfo(tp, _dbfs(tp), float(pk_d[0].item()), int(lim_d[0].item()), float(limit_db), wa, wr)

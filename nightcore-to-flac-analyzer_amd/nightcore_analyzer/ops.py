@@ -401,6 +401,174 @@ def flac_decode(eng: Engine, blobs: Sequence[bytes], **kw) -> List[Tuple[np.ndar
     return out
 
 
+# ------------------------------------------------------------------ FLAC encode (flac_enc.hip)
+FLAC_ENC_STATUS = {1: "table row outside the buffers or the format's limits", 2: "sample outside the sample size"}
+FLAC_SUBFRAME_TYPES = ("constant", "verbatim", "fixed", "lpc")
+
+
+def flac_slot_bytes(channels: int, block: int, bits: int) -> int:
+    """Bytes of one frame's slot: the all-VERBATIM bound ``nc_flac_encode`` documents."""
+    return (16 + (channels * (8 + block * (bits + 1)) + 7) // 8 + 2 + 3) // 4 * 4
+
+
+def _per_stream(value, n: int, what: str) -> List[int]:
+    vals = [int(value)] * n if isinstance(value, (int, np.integer)) else [int(v) for v in value]
+    if len(vals) != n:
+        raise ValueError(f"flac_encode: one {what} per stream is needed")
+    return vals
+
+
+def flac_encode_device(eng: Engine, src: DeviceSignals, streams, bits, rate, block: int = 4096, level: int = 1,
+                       names: Optional[Sequence[str]] = None):
+    """Encode streams resident in HBM as FLAC frames in one ``nc_flac_encode`` launch (one wave
+    per frame) and one ``nc_flac_pack``: (frame bytes per stream, info dict per stream).
+
+    ``src``: a ``DeviceSignals`` whose buffer is float32 (quantised by the kernel:
+    clamp(rint(x 2^(bits-1))), round half to even, ``nc_f32_to_pcm16``'s rule) or int32 (samples
+    already inside ``bits``).  ``streams``: the channel count of every stream (an int for all);
+    stream s is that many consecutive, equally long, equally spaced signals of ``src``.  ``bits``
+    (4-24) and ``rate`` (1 .. 2^20 - 1): an int for all streams or one per stream.  ``block``:
+    16 .. 16384, the fixed block size; ``level`` 0 (CONSTANT / VERBATIM / FIXED) or 1 (plus LPC
+    1-8; never longer than level 0).  info: ``frame_bytes`` (int32 per frame), ``min_frame`` /
+    ``max_frame``, ``clipped`` (samples clamped by the quantiser), ``records`` (int32 [frames, 25]:
+    assignment, then type / order / partition order per channel), ``pcm`` (the device int32
+    samples [channels, total]), ``channels`` / ``bits`` / ``rate`` / ``total`` / ``block``.
+    Only the packed bytes and the per-frame arrays are downloaded.  A frame whose status is not 0
+    raises ValueError naming the stream and the frame."""
+    n_sig = src.n_files
+    chans = [int(streams)] * (n_sig // max(1, int(streams))) if isinstance(streams, (int, np.integer)) \
+        else [int(c) for c in streams]
+    n_streams = len(chans)
+    if any(c < 1 or c > 8 for c in chans) or sum(chans) != n_sig:
+        raise ValueError("flac_encode: every stream needs 1 .. 8 channels and the streams must use every signal")
+    bits_s, rate_s = _per_stream(bits, n_streams, "sample size"), _per_stream(rate, n_streams, "sample rate")
+    block, level = int(block), int(level)
+    if not 16 <= block <= 16384:
+        raise ValueError(f"flac_encode: block size {block} outside 16 .. 16384")
+    if level not in (0, 1):
+        raise ValueError(f"flac_encode: level {level} is not 0 or 1")
+    for b, r in zip(bits_s, rate_s):
+        if not 4 <= b <= 24:
+            raise ValueError(f"flac_encode: {b} bits per sample outside 4 .. 24")
+        if not 0 < r < 1 << 20:
+            raise ValueError(f"flac_encode: sample rate {r} outside 1 .. 2^20 - 1")
+    if src.buf.dtype not in (torch.float32, torch.int32):
+        raise ValueError("flac_encode: the samples must be float32 or int32")
+    names = [f"stream {i}" for i in range(n_streams)] if names is None else [str(n) for n in names]
+    files = np.zeros((max(1, n_streams), 8), np.int64)
+    rows, infos = [], []
+    first_sig = slot_pos = 0
+    for s, ch in enumerate(chans):
+        off = np.asarray(src.off[first_sig:first_sig + ch], np.int64)
+        lens = np.asarray(src.length[first_sig:first_sig + ch], np.int64)
+        first_sig += ch
+        total = int(lens[0])
+        stride = int(off[1] - off[0]) if ch > 1 else max(total, 1)
+        if np.any(lens != total) or (ch > 1 and (stride < total or np.any(np.diff(off) != stride))):
+            raise ValueError(f"{names[s]}: the channels of a stream must be equally long and equally spaced")
+        if total >= 1 << 36:
+            raise ValueError(f"{names[s]}: {total} samples do not fit STREAMINFO")
+        files[s] = (int(off[0]), stride, ch, bits_s[s], rate_s[s], total, 0, 0)
+        n_fr = -(-total // block)
+        need = flac_slot_bytes(ch, block, bits_s[s])
+        t = np.zeros((n_fr, 8), np.int64)
+        t[:, 0] = s
+        t[:, 1] = np.arange(n_fr) * block
+        t[:, 2] = np.minimum(block, total - t[:, 1])
+        t[:, 3] = np.arange(n_fr)
+        t[:, 4] = slot_pos + np.arange(n_fr) * need
+        slot_pos += n_fr * need
+        rows.append(t)
+        infos.append(dict(channels=ch, bits=bits_s[s], rate=rate_s[s], total=total, block=block, _off=int(off[0]),
+                          _stride=stride))
+    frames = np.concatenate(rows) if rows else np.zeros((0, 8), np.int64)
+    n_frames = len(frames)
+    is_float = src.buf.dtype == torch.float32
+    q = torch.empty(src.buf.numel(), dtype=torch.int32, device=eng.dev) if is_float else src.buf
+    nf = max(1, n_frames)
+    fb = torch.zeros(nf, dtype=torch.int32, device=eng.dev)
+    rec = torch.zeros(nf * 25, dtype=torch.int32, device=eng.dev)
+    clipped = torch.zeros(nf, dtype=torch.int32, device=eng.dev)
+    status = torch.zeros(nf, dtype=torch.int32, device=eng.dev)
+    packed_h = np.zeros(0, np.uint8)
+    fb_h = cl_h = np.zeros(0, np.int32)
+    rec_h = np.zeros((0, 25), np.int32)
+    if n_frames:
+        up = _Upload()
+        up.add("frames", frames, np.int64)
+        up.add("files", files, np.int64)
+        d = up.commit(eng.dev)
+        slots = torch.empty(slot_pos, dtype=torch.uint8, device=eng.dev)
+        eng.call("nc_flac_encode", None if is_float else src.buf.data_ptr(), src.buf.data_ptr() if is_float else None,
+                 q.data_ptr() if is_float else None, src.buf.numel(), d["frames"].data_ptr(), n_frames,
+                 d["files"].data_ptr(), n_streams, level, slots.data_ptr(), slot_pos, fb.data_ptr(), rec.data_ptr(),
+                 clipped.data_ptr(), status.data_ptr(), eng.stream())
+        ends = torch.cumsum(fb, 0, dtype=torch.int64)
+        offsets = ends - fb
+        small = torch.cat([fb, status, clipped, rec]).cpu().numpy()      # the one synchronisation before the pack
+        fb_h, st_h, cl_h, rec_h = small[:nf], small[nf:2 * nf], small[2 * nf:3 * nf], small[3 * nf:].reshape(nf, 25)
+        bad = np.flatnonzero(st_h[:n_frames])
+        if len(bad):
+            g = int(bad[0])
+            s = int(frames[g, 0])
+            code = int(st_h[g])
+            raise ValueError(f"{names[s]}: frame {int(frames[g, 3])} (samples {int(frames[g, 1])} .. "
+                             f"{int(frames[g, 1] + frames[g, 2])}): {FLAC_ENC_STATUS.get(code, code)}")
+        out_bytes = (int(fb_h.sum(dtype=np.int64)) + 3) // 4 * 4
+        out = torch.empty(max(4, out_bytes), dtype=torch.uint8, device=eng.dev)
+        eng.call("nc_flac_pack", slots.data_ptr(), slot_pos, d["frames"].data_ptr(), n_frames, fb.data_ptr(),
+                 offsets.data_ptr(), out.data_ptr(), out_bytes, eng.stream())
+        packed_h = out.cpu().numpy()
+    blobs = []
+    g = pos = 0
+    for s, info in enumerate(infos):
+        n_fr = len(rows[s])
+        sizes = fb_h[g:g + n_fr] if n_fr else np.zeros(0, np.int32)
+        n_bytes = int(sizes.sum(dtype=np.int64))
+        blobs.append(packed_h[pos:pos + n_bytes].tobytes())
+        o, stride, ch, total = info.pop("_off"), info.pop("_stride"), info["channels"], info["total"]
+        info.update(frame_bytes=sizes.copy(), min_frame=int(sizes.min()) if n_fr else 0,
+                    max_frame=int(sizes.max()) if n_fr else 0,
+                    clipped=int(cl_h[g:g + n_fr].sum()) if n_fr else 0,
+                    records=rec_h[g:g + n_fr].copy() if n_fr else np.zeros((0, 25), np.int32),
+                    pcm=torch.as_strided(q, (ch, total), (stride, 1), o))
+        g += n_fr
+        pos += n_bytes
+    return blobs, infos
+
+
+def flac_encode(eng: Engine, arrays: Sequence[np.ndarray], bits, rate, block: int = 4096, level: int = 1):
+    """[(frame bytes, info)] of integer arrays [channels, n] (or [n]), one stream each, by
+    ``flac_encode_device``; ``info["pcm"]`` comes back as a host array."""
+    arrs = [np.atleast_2d(np.asarray(a)) for a in arrays]
+    for a in arrs:
+        if a.dtype.kind not in "iu" or a.ndim != 2:
+            raise ValueError("flac_encode: integer arrays [channels, n] are needed")
+    off, length, pos = [], [], 0
+    for a in arrs:
+        stride = (a.shape[1] + _ALIGN - 1) // _ALIGN * _ALIGN
+        off += [pos + c * stride for c in range(a.shape[0])]
+        length += [a.shape[1]] * a.shape[0]
+        pos += a.shape[0] * stride
+    host = torch.zeros(max(_ALIGN, pos), dtype=torch.int32, pin_memory=True)
+    hv = host.numpy()
+    at = 0
+    for a in arrs:
+        if a.size and (a.min() < -(1 << 31) or a.max() >= 1 << 31):
+            raise ValueError("flac_encode: a sample does not fit 32 bits")
+        for c in range(a.shape[0]):
+            hv[off[at]:off[at] + a.shape[1]] = a[c]
+            at += 1
+    sig = DeviceSignals(host.to(eng.dev, non_blocking=True), np.asarray(off, np.int64), np.asarray(length, np.int64))
+    blobs, infos = flac_encode_device(eng, sig, [a.shape[0] for a in arrs], bits, rate, block, level)
+    out = []
+    for blob, info in zip(blobs, infos):
+        info = dict(info)
+        info["pcm"] = info["pcm"].cpu().numpy()
+        out.append((blob, info))
+    return out
+
+
 # ------------------------------------------------------------------ speed render (speed.hip)
 def speed_plan(factor: float, lengths: Sequence[int]) -> Tuple[int, np.ndarray]:
     """(P, n_out[file]) of a speed render: P = round(factor 1e6), n_out = ceil(n 1e6 / P), from

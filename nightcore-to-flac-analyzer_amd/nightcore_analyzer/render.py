@@ -8,7 +8,8 @@ renderer's definition is this project's own (``nc_speed_render`` in
 include/ncgpu.h): a Kaiser-windowed sinc (beta 10.06, 32 zero crossings a side, cut-off at
 0.9 of the lower Nyquist) evaluated at the exact rational position m P / 10^6 of every output.
 
-* ``speed`` / ``speed_file`` — the render of an array / of every channel of a WAV file
+* ``speed`` / ``speed_file`` — the render of an array / of every channel of a WAV or FLAC file,
+  written as WAV or (destination ``.flac``) as FLAC encoded on the device
   (``limit_db``: with the true-peak limiter on the resident render, loudness.py).
 * ``refine_speed`` — render, re-analyse, correct; the render stays in HBM between the two.
 * ``quantize_factor`` / ``hqnc_path`` — the six-decimal factor and the output naming rule.
@@ -76,6 +77,18 @@ class RenderInfo:
         return self.peak_dbfs >= 0.0
 
 
+def _write_flac_render(dst_path, eng, out, ch: int, n_out: int, sr: int, fmt: str):
+    """The first ``n_out`` samples of the ``ch`` resident channels ``out`` as the FLAC file
+    ``dst_path``, quantised and encoded on the device (no float download): a "pcm<b>" source with
+    b <= 16 gives 16 bits, any other 24.  Returns (sample format, samples the quantiser clamped)."""
+    from .engine import DeviceSignals
+    from .io import flac_bits, write_flac_device
+    bits = flac_bits(fmt)
+    sig = DeviceSignals(out.buf, np.asarray(out.off[:ch], np.int64), np.full(ch, n_out, np.int64))
+    info = write_flac_device(dst_path, eng, sig, sr, bits)
+    return f"pcm{bits}", info["clipped"]
+
+
 def speed(y: np.ndarray, factor: float, sr: Optional[int] = None) -> np.ndarray:
     """The mono signal ``y`` played ``factor`` times faster (float32, ceil(len / factor')
     samples at the same rate, factor' = ``quantize_factor(factor)``).  ``sr`` is accepted for
@@ -91,7 +104,9 @@ def speed_file(src_path, dst_path, factor: float, limit_db: Optional[float] = No
                attack_ms: float = 5.0, release_ms: float = 50.0) -> RenderInfo:
     """Render every channel of the WAV or FLAC file ``src_path`` at its own rate and write
     ``dst_path``: a 16-bit PCM source gives a 16-bit PCM file (quantised on the device,
-    ``nc_f32_to_pcm16``), anything else a float32 file.  With a ceiling ``limit_db`` (dBFS,
+    ``nc_f32_to_pcm16``), anything else a float32 file; a ``dst_path`` ending in ``.flac`` is
+    written as FLAC, encoded on the device from the resident render (16 bits for a source of at
+    most 16 bits, else 24; ``sample_format`` "pcm16" / "pcm24").  With a ceiling ``limit_db`` (dBFS,
     at most 0) the true-peak limiter (``nc_true_peak_limit``, channels linked) runs on the
     resident render before the quantisation; the render does not leave HBM in between."""
     from .engine import get_engine
@@ -109,17 +124,20 @@ def speed_file(src_path, dst_path, factor: float, limit_db: Optional[float] = No
         out, tp_d, pk_d, lim_d = true_peak_limit_device(eng, out, ch, float(limit_db), wa, wr, in_place=True)
         peak_d = pk_d
         extra = dict(true_peak=tp_d, limited_samples=lim_d, limit_db=float(limit_db))
-    if fmt == "pcm16":
+    if Path(dst_path).suffix.lower() == ".flac":
+        out_fmt, clipped = _write_flac_render(dst_path, eng, out, ch, n_out, sr, fmt)
+    elif fmt == "pcm16":
         q, _, clipped_d = f32_to_pcm16_device(eng, out, interleave=True)
         frames = q[:ch * n_out].cpu().numpy().reshape(n_out, ch).T
         clipped = int(clipped_d.sum().item())
         out_fmt = "pcm16"
+        write_wav(dst_path, frames, sr, out_fmt)
     else:
         hy = out.buf.cpu().numpy()
         frames = np.stack([hy[o:o + n_out] for o in out.off])
         clipped = int(np.count_nonzero(np.abs(frames) >= 1.0))
         out_fmt = "float32"
-    write_wav(dst_path, frames, sr, out_fmt)
+        write_wav(dst_path, frames, sr, out_fmt)
     peak = float(peak_d.max().item()) if ch else 0.0
     if extra:
         extra.update(true_peak=float(extra["true_peak"][0].item()),
@@ -238,7 +256,8 @@ def pitch_file(src_path, dst_path, semitones: float, limit_db: Optional[float] =
                attack_ms: float = 5.0, release_ms: float = 50.0) -> PitchInfo:
     """Shift every channel of the WAV or FLAC file ``src_path`` by ``semitones`` at its own rate and
     write ``dst_path`` (same rate, channels and length): a 16-bit PCM source gives a 16-bit PCM
-    file (``nc_f32_to_pcm16``), anything else a float32 file.  With a ceiling ``limit_db`` the
+    file (``nc_f32_to_pcm16``), anything else a float32 file; a ``.flac`` destination is encoded on
+    the device as in ``speed_file``.  With a ceiling ``limit_db`` the
     true-peak limiter runs on the resident result first, as in ``speed_file``."""
     from .engine import get_engine
     from .ops import f32_to_pcm16_device, limiter_windows, pitch_shift_device, true_peak_limit_device
@@ -255,17 +274,20 @@ def pitch_file(src_path, dst_path, semitones: float, limit_db: Optional[float] =
         out, tp_d, pk_d, lim_d = true_peak_limit_device(eng, out, ch, float(limit_db), wa, wr, in_place=True)
         peak_d = pk_d
         extra = dict(true_peak=tp_d, limited_samples=lim_d, limit_db=float(limit_db))
-    if fmt == "pcm16":
+    if Path(dst_path).suffix.lower() == ".flac":
+        out_fmt, clipped = _write_flac_render(dst_path, eng, out, ch, n_out, sr, fmt)
+    elif fmt == "pcm16":
         q, _, clipped_d = f32_to_pcm16_device(eng, out, interleave=True)
         frames = q[:ch * n_out].cpu().numpy().reshape(n_out, ch).T
         clipped = int(clipped_d.sum().item())
         out_fmt = "pcm16"
+        write_wav(dst_path, frames, sr, out_fmt)
     else:
         hy = out.buf.cpu().numpy()
         frames = np.stack([hy[o:o + n_out] for o in out.off])
         clipped = int(np.count_nonzero(np.abs(frames) >= 1.0))
         out_fmt = "float32"
-    write_wav(dst_path, frames, sr, out_fmt)
+        write_wav(dst_path, frames, sr, out_fmt)
     peak = float(peak_d.max().item()) if ch else 0.0
     if extra:
         extra.update(true_peak=float(extra["true_peak"][0].item()),
