@@ -607,6 +607,48 @@ int nc_pv_stretch(nc_ctx* ctx, const float* x, const int64_t* in_off, const int6
                   size_t ws_bytes, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Identity phase locking with linked channels for the stretch above (opt-in;
+ * DESIGN.md section 4, "Phase locking"; tests/pvoc_lock_ref.py).  Same
+ * conventions: device pointers unless stated, 0 / -1 / -2, no allocation, no
+ * host synchronisation, fixed launch counts, bit-identical run to run and
+ * batch to single.
+ * nc_pv_analyze_u: nc_pv_analyze plus u[frame][1025][2] = ph(A) (one launch);
+ *     mag, v and empty are bit-identical to nc_pv_analyze's.  v is nullable here:
+ *     the frames Hs earlier are then not transformed (a linked channel needs
+ *     mag and u only).
+ * nc_pv_lock: owner[frame][1025] (uint16, nullable) and the locked scan phi from
+ *     mag, u, v and empty (four launches: peaks / owners / M per frame, then the
+ *     tile, carry and apply passes of the scan with a gather).  max_frames = the
+ *     largest K; ws: at least nc_pv_lock_ws_bytes(total_frames, n_files) bytes
+ *     (host only), 16-byte aligned.
+ * nc_pv_mid_sum: mid[mid_off[g] + i] = ((x_0[i] + x_1[i]) + ...) in float32 over
+ *     the channels group_first[g] .. group_first[g + 1] - 1 of group g (one
+ *     launch).  host_len / host_first: HOST copies of sig_len / group_first;
+ *     -2 when the channels of a group differ in length.
+ * nc_pv_rotate: phi of every channel frame from its group's locked scan psi and
+ *     analysis phasors u_mid (rows laid out by mid_base[groups + 1], the frame
+ *     bases of the sums) and the channel's own u (rows by frame_base):
+ *     ph(psi u conj(u_mid)) in f64; a group of one channel copies psi (one launch).
+ * The locked stretch is nc_pv_analyze_u, nc_pv_lock and nc_pv_synth for
+ * unlinked files (7 launches), and nc_pv_mid_sum, nc_pv_analyze_u of the
+ * channels and of the sums, nc_pv_lock of the sums, nc_pv_rotate and
+ * nc_pv_synth for linked groups (10 launches).
+ * ------------------------------------------------------------------------- */
+int nc_pv_analyze_u(nc_ctx* ctx, const float* x, const int64_t* in_off, const int64_t* in_len,
+                    const int64_t* frame_base, int n_files, int64_t total_frames, int64_t p, float* mag, float* v,
+                    uint8_t* empty, float* u, void* stream);
+size_t nc_pv_lock_ws_bytes(int64_t total_frames, int n_files);
+int nc_pv_lock(nc_ctx* ctx, const float* mag, const float* u, const float* v, const uint8_t* empty,
+               const int64_t* frame_base, int n_files, int64_t total_frames, int64_t max_frames, float* phi,
+               uint16_t* owner, void* ws, size_t ws_bytes, void* stream);
+int nc_pv_mid_sum(nc_ctx* ctx, const float* x, const int64_t* sig_off, const int64_t* sig_len,
+                  const int* group_first, const int64_t* host_len, const int* host_first, int n_groups, float* mid,
+                  const int64_t* mid_off, void* stream);
+int nc_pv_rotate(nc_ctx* ctx, const float* psi, const float* u_mid, const int64_t* mid_base, const float* u,
+                 const int64_t* frame_base, const int* group_first, int n_files, int n_groups, int64_t total_frames,
+                 float* phi, void* stream);
+
+/* -------------------------------------------------------------------------
  * MELODIA front end (opt-in; replaces the frame-level part of essentia's
  * PredominantPitchMelodia that pitch.estimate_pitch_melodia calls,
  * pitch.py:210-215: frameSize 2048, hopSize 128).  PARITY UNPINNED: essentia is

@@ -121,7 +121,17 @@ int pv_plan(int64_t P, const int64_t* n_in, int n_files, int64_t* ns_out, int64_
 size_t pv_scan_ws_bytes(int64_t total_frames, int n_files);
 int launch_pv_analyze(Context& ctx, const float* x, const int64_t* in_off, const int64_t* in_len,
                       const int64_t* frame_base, int n_files, int64_t total_frames, int64_t P, float* mag, float2* V,
-                      uint8_t* empty, hipStream_t st);
+                      uint8_t* empty, float2* U, bool with_u, hipStream_t st);
+size_t pv_lock_ws_bytes(int64_t total_frames, int n_files);
+int launch_pv_lock(Context& ctx, const float* mag, const float2* U, const float2* V, const uint8_t* empty,
+                   const int64_t* frame_base, int n_files, int64_t total_frames, int64_t max_frames, float2* phi,
+                   uint16_t* owner, void* ws, size_t ws_bytes, hipStream_t st);
+int launch_pv_mid_sum(Context& ctx, const float* x, const int64_t* sig_off, const int64_t* sig_len,
+                      const int* group_first, const int64_t* host_len, const int* host_first, int n_groups,
+                      float* mid, const int64_t* mid_off, hipStream_t st);
+int launch_pv_rotate(Context& ctx, const float2* psi, const float2* u_mid, const int64_t* mid_base, const float2* u,
+                     const int64_t* frame_base, const int* group_first, int n_files, int n_groups,
+                     int64_t total_frames, float2* phi, hipStream_t st);
 int launch_pv_scan(Context& ctx, const float2* V, const uint8_t* empty, const int64_t* frame_base, int n_files,
                    int64_t total_frames, int64_t max_frames, float2* phi, void* ws, size_t ws_bytes, hipStream_t st);
 int launch_pv_synth(Context& ctx, const float* mag, const float2* phi, const int64_t* in_len,
@@ -720,7 +730,50 @@ int nc_pv_analyze(nc_ctx* ctx, const float* x, const int64_t* in_off, const int6
   CHECK_CTX(ctx);
   SET_DEVICE(ctx);
   return nc::launch_pv_analyze(ctx->c, x, in_off, in_len, frame_base, n_files, total_frames, p, mag,
-                               reinterpret_cast<float2*>(v), empty, (hipStream_t)stream);
+                               reinterpret_cast<float2*>(v), empty, nullptr, false, (hipStream_t)stream);
+}
+
+int nc_pv_analyze_u(nc_ctx* ctx, const float* x, const int64_t* in_off, const int64_t* in_len,
+                    const int64_t* frame_base, int n_files, int64_t total_frames, int64_t p, float* mag, float* v,
+                    uint8_t* empty, float* u, void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_pv_analyze(ctx->c, x, in_off, in_len, frame_base, n_files, total_frames, p, mag,
+                               reinterpret_cast<float2*>(v), empty, reinterpret_cast<float2*>(u), true,
+                               (hipStream_t)stream);
+}
+
+size_t nc_pv_lock_ws_bytes(int64_t total_frames, int n_files) {
+  return total_frames < 0 || n_files < 0 ? 0 : nc::pv_lock_ws_bytes(total_frames, n_files);
+}
+
+int nc_pv_lock(nc_ctx* ctx, const float* mag, const float* u, const float* v, const uint8_t* empty,
+               const int64_t* frame_base, int n_files, int64_t total_frames, int64_t max_frames, float* phi,
+               uint16_t* owner, void* ws, size_t ws_bytes, void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_pv_lock(ctx->c, mag, reinterpret_cast<const float2*>(u), reinterpret_cast<const float2*>(v),
+                            empty, frame_base, n_files, total_frames, max_frames, reinterpret_cast<float2*>(phi),
+                            owner, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int nc_pv_mid_sum(nc_ctx* ctx, const float* x, const int64_t* sig_off, const int64_t* sig_len,
+                  const int* group_first, const int64_t* host_len, const int* host_first, int n_groups, float* mid,
+                  const int64_t* mid_off, void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_pv_mid_sum(ctx->c, x, sig_off, sig_len, group_first, host_len, host_first, n_groups, mid,
+                               mid_off, (hipStream_t)stream);
+}
+
+int nc_pv_rotate(nc_ctx* ctx, const float* psi, const float* u_mid, const int64_t* mid_base, const float* u,
+                 const int64_t* frame_base, const int* group_first, int n_files, int n_groups, int64_t total_frames,
+                 float* phi, void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_pv_rotate(ctx->c, reinterpret_cast<const float2*>(psi), reinterpret_cast<const float2*>(u_mid),
+                              mid_base, reinterpret_cast<const float2*>(u), frame_base, group_first, n_files,
+                              n_groups, total_frames, reinterpret_cast<float2*>(phi), (hipStream_t)stream);
 }
 
 int nc_pv_scan(nc_ctx* ctx, const float* v, const uint8_t* empty, const int64_t* frame_base, int n_files,
@@ -776,7 +829,8 @@ int nc_pv_stretch(nc_ctx* ctx, const float* x, const int64_t* in_off, const int6
   uint8_t* empty = total_frames > 0 ? reinterpret_cast<uint8_t*>(w + ws_off[4]) : nullptr;
   void* scan_ws = total_frames > 0 ? static_cast<void*>(w + ws_off[5]) : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  int rc = nc::launch_pv_analyze(ctx->c, x, in_off, in_len, frame_base, n_files, total_frames, p, mag, v, empty, st);
+  int rc = nc::launch_pv_analyze(ctx->c, x, in_off, in_len, frame_base, n_files, total_frames, p, mag, v, empty,
+                                 nullptr, false, st);
   if (rc) return rc;
   rc = nc::launch_pv_scan(ctx->c, v, empty, frame_base, n_files, total_frames, max_frames, phi, scan_ws,
                           total_frames > 0 ? ws_bytes - (size_t)ws_off[5] : 0, st);

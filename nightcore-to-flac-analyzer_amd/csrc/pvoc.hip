@@ -3,7 +3,8 @@
 // half is the speed render of speed.hip at the same ratio).  PARITY UNPINNED: rubberband is
 // absent and the reference holds no pitch shifter; the definition is the project's own
 // (DESIGN.md §4 "Pitch shift", tests/pvoc_ref.py).  Plain phase vocoder: no transient
-// detection, no phase locking.
+// detection, no phase locking (identity phase locking with linked channels is opt-in: the last
+// section of this file).
 //   N = 2048, Hs = 512, Q = 1e6, W = periodic Hann, P = round(2^(S/12) Q) in [Q/2, 2Q],
 //   Ns = ceil(n P / Q), K = ceil(Ns / Hs) + 3 frames, u_k = ((k - 1) Hs Q) div P (floor),
 //   A_k = rfft(x[u_k - N/2 + i] W[i]), B_k the frame Hs samples earlier, mag_k = |A_k|,
@@ -159,6 +160,7 @@ struct PvAnaArgs {
   const float2* tw;
   const float* hann;
   unsigned long long* span;
+  float2* U;  // WITH_U only: ph(A_k); V may then be null (B_k is not transformed)
 };
 
 static size_t pv_analysis_lds() {
@@ -168,6 +170,9 @@ static size_t pv_synth_lds() {
   return ((size_t)pv_al4(PvTw::size) + (size_t)PV_WAVES * LdsSize<1024>::value) * sizeof(float2);
 }
 
+// WITH_U: the analysis phasor U_k = ph(A_k) leaves as well (phase locking, below); mag, V and empty
+// are computed by the same instructions in both variants.
+template <bool WITH_U>
 __global__ __launch_bounds__(PV_THREADS) void pv_analysis_kernel(PvAnaArgs a) {
   const Span span_(a.span);
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -211,7 +216,8 @@ __global__ __launch_bounds__(PV_THREADS) void pv_analysis_kernel(PvAnaArgs a) {
     const bool reset = k == 0 || pv_span_empty(x, L, pv_centre(k - 1, a.P), lane);
     if (lane == 0) a.empty[g] = empty ? 1 : 0;
 
-    if (!reset) pv_rfft<0>(xv, hann2, fftbuf, sh_tw, lane, spec_b);
+    const bool with_v = !WITH_U || a.V != nullptr;  // kernel-uniform
+    if (!reset && with_v) pv_rfft<0>(xv, hann2, fftbuf, sh_tw, lane, spec_b);
     pv_rfft<4>(xv, hann2, fftbuf, sh_tw, lane, fftbuf);
     const float2* spec_a = fftbuf;
 
@@ -220,6 +226,9 @@ __global__ __launch_bounds__(PV_THREADS) void pv_analysis_kernel(PvAnaArgs a) {
     auto bin = [&](int b) {
       const float2 A = spec_a[b];
       const float ma = __fsqrt_rn(fmaf(A.x, A.x, A.y * A.y));
+      mrow[b] = ma;
+      if (WITH_U) a.U[g * PV_BINS + b] = pv_ph(A, ma);
+      if (!with_v) return;
       float2 v;
       if (reset) {
         v = pv_ph(A, ma);
@@ -228,7 +237,6 @@ __global__ __launch_bounds__(PV_THREADS) void pv_analysis_kernel(PvAnaArgs a) {
         const float2 z = make_float2(fmaf(A.x, B.x, A.y * B.y), fmaf(A.y, B.x, -(A.x * B.y)));
         v = pv_ph(z, __fsqrt_rn(fmaf(z.x, z.x, z.y * z.y)));
       }
-      mrow[b] = ma;
       vrow[b] = v;
     };
 #pragma unroll
@@ -240,7 +248,7 @@ __global__ __launch_bounds__(PV_THREADS) void pv_analysis_kernel(PvAnaArgs a) {
 
 int launch_pv_analyze(Context& ctx, const float* x, const int64_t* in_off, const int64_t* in_len,
                       const int64_t* frame_base, int n_files, int64_t total_frames, int64_t P, float* mag, float2* V,
-                      uint8_t* empty, hipStream_t st) {
+                      uint8_t* empty, float2* U, bool with_u, hipStream_t st) {
   if (P < PV_Q / 2 || P > 2 * PV_Q) {
     set_error("pv_analyze: ratio outside [0.5, 2]");
     return -2;
@@ -250,17 +258,21 @@ int launch_pv_analyze(Context& ctx, const float* x, const int64_t* in_off, const
     return -2;
   }
   if (n_files == 0 || total_frames == 0) return 0;
-  if (!x || !in_off || !in_len || !frame_base || !mag || !V || !empty) {
+  if (!x || !in_off || !in_len || !frame_base || !mag || (!V && !with_u) || !empty || (with_u && !U)) {
     set_error("pv_analyze: null argument");
     return -2;
   }
-  PvAnaArgs a{x, in_off, in_len, frame_base, n_files, total_frames, P, mag, V, empty, ctx.t.tw, ctx.t.hann2048, nullptr};
+  PvAnaArgs a{x, in_off, in_len, frame_base, n_files, total_frames, P, mag, V, empty, ctx.t.tw, ctx.t.hann2048, nullptr,
+              with_u ? U : nullptr};
   const int64_t n_groups = (total_frames + PV_WAVES - 1) / PV_WAVES;
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(n_groups, ctx.num_cu));
   {
     KTimer kt_(ctx, "pv_analysis", st);
     a.span = kt_.span();
-    hipLaunchKernelGGL(pv_analysis_kernel, dim3(grid), dim3(PV_THREADS), pv_analysis_lds(), st, a);
+    if (with_u)
+      hipLaunchKernelGGL(pv_analysis_kernel<true>, dim3(grid), dim3(PV_THREADS), pv_analysis_lds(), st, a);
+    else
+      hipLaunchKernelGGL(pv_analysis_kernel<false>, dim3(grid), dim3(PV_THREADS), pv_analysis_lds(), st, a);
   }
   NC_HIP(hipGetLastError());
   return 0;
@@ -534,6 +546,462 @@ int launch_pv_synth(Context& ctx, const float* mag, const float2* phi, const int
     hipLaunchKernelGGL(pv_ola_kernel, dim3((unsigned)((max_ns + PV_OLA_OUT - 1) / PV_OLA_OUT), (unsigned)n_files),
                        dim3(256), 0, st,
                        frames, in_len, frame_base, P, s, out_off, reinterpret_cast<unsigned*>(peak), kt_.span());
+  }
+  NC_HIP(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------------ phase locking
+// Identity phase locking with linked channels (opt-in; DESIGN.md §4 "Phase locking",
+// tests/pvoc_lock_ref.py).  With U_k = ph(A_k):
+//   peaks    b is a peak iff mag[b] > mag[b-1], mag[b-2] and mag[b] >= mag[b+1], mag[b+2] (neighbours
+//            outside 0..1024 ignored); a frame without one has the single peak 0
+//   owners   o_k[b]: between consecutive peaks p < q, b <= (p + q) div 2 belongs to p, the rest to q
+//   M_k[b] = V_k[b] when b == o (and on a reset frame), else V_k[o] U_k[b] conj(U_k[o])
+//   Phi_k  = V_k on a reset frame, else Phi_k[b] = ph(Phi_{k-1}[o_k[b]] M_k[b])
+//   linked   the channels of a group follow the scan Psi of their float32 sum m:
+//            Phi^c_k[b] = ph(Psi_k[b] U^c_k[b] conj(U^m_k[b])); a group of one channel is Psi itself.
+//   pv_lock_prep   one wave per frame, lanes along bins: the peak test leaves as 17 ballots (the
+//                  frame's peak bitmap in SGPRs), the nearest peak below and above each bin comes
+//                  from clz / ffs on its word; writes owner (uint16) and M (f64 product, stored f32).
+//   pv_lock_tile / pv_lock_carry / pv_lock_apply   the plain scan's three passes, generalised by a
+//                  source bin: a workgroup walks the PV_TILE frames of one (file, tile) with the
+//                  whole row in LDS (double-buffered: frame k gathers from frame k - 1's row); each
+//                  bin carries (source bin at the tile start or PV_ABS after a reset, f64 product).
+//                  One workgroup per file walks the tile aggregates with the same gather.
+//   pv_mid_sum / pv_rotate   the linked channels' sum, and their phases from Psi (bandwidth).
+// Fixed launch counts, no atomics, no allocation, no host synchronisation; the association depends
+// on the file's own frame index alone.
+constexpr unsigned PV_ABS = 0xffffu;  // source marker: the product is absolute (a reset was met)
+constexpr int PV_LROW = PV_BINS + 3;  // LDS row stride
+constexpr int PV_LBPT = 5;            // bins per thread of a 256-thread workgroup (5 x 256 >= 1025)
+constexpr int PV_CDEPTH = 4;          // tile aggregates in flight ahead of the carry walk
+
+struct PvLockArgs {
+  const float* mag;
+  const float2* U;
+  const float2* V;
+  const uint8_t* empty;
+  const int64_t* frame_base;
+  int n_files;
+  int64_t total_frames;
+  uint16_t* owner;  // [frame][bin]
+  float2* M;        // [frame][bin]
+  float2* phi;
+  double2* agg;     // [row][bin] tile aggregates
+  uint16_t* asrc;   // [row][bin] their source bins
+  double2* carry;   // [row][bin] Phi of the frame before each tile
+  unsigned long long* span;
+};
+
+static size_t pv_lock_ws_layout(int64_t total_frames, int n_files, size_t off[5]) {
+  const size_t t = (size_t)total_frames, rows = (size_t)pv_scan_rows(total_frames, n_files);
+  const size_t sizes[5] = {t * PV_BINS * sizeof(float2), t * PV_BINS * sizeof(uint16_t),
+                           rows * PV_BINS * sizeof(double2), rows * PV_BINS * sizeof(double2),
+                           rows * PV_BINS * sizeof(uint16_t)};
+  size_t o = 0;
+  for (int i = 0; i < 5; ++i) {
+    off[i] = o;
+    o += al256(sizes[i]);
+  }
+  return o;
+}
+// M, owner, agg, carry, asrc
+size_t pv_lock_ws_bytes(int64_t total_frames, int n_files) {
+  size_t off[5];
+  return pv_lock_ws_layout(total_frames, n_files, off);
+}
+
+__device__ __forceinline__ double2 pv_mul64(double2 p, double2 v) {
+  return make_double2(p.x * v.x - p.y * v.y, p.x * v.y + p.y * v.x);
+}
+
+__global__ __launch_bounds__(256) void pv_lock_prep_kernel(PvLockArgs a) {
+  const Span span_(a.span);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t g = (int64_t)blockIdx.x * 4 + wave;
+  if (g >= a.total_frames) return;
+  const int f = uniform32(seg_of(a.frame_base, a.n_files, g));
+  const bool reset = g == uniform64(a.frame_base[f]) || a.empty[g - 1] != 0;
+  const float* m = a.mag + g * PV_BINS;
+
+  unsigned long long mask[17];
+  bool any = false;
+#pragma unroll
+  for (int j = 0; j < 17; ++j) {
+    const int b = 64 * j + lane;
+    bool pk = false;
+    if (b < PV_BINS) {
+      const float m0 = m[b];
+      pk = (b < 1 || m0 > m[b - 1]) && (b < 2 || m0 > m[b - 2]) && (b + 1 >= PV_BINS || m0 >= m[b + 1]) &&
+           (b + 2 >= PV_BINS || m0 >= m[b + 2]);
+    }
+    mask[j] = __ballot(pk);
+    any |= mask[j] != 0;
+  }
+  if (!any) mask[0] = 1;  // non-finite magnitudes only: the single peak 0
+  // the nearest peak in the words below / above each word (-1: none)
+  int below[17], above[17];
+  int last = -1;
+#pragma unroll
+  for (int j = 0; j < 17; ++j) {
+    below[j] = last;
+    if (mask[j]) last = 64 * j + 63 - __clzll((long long)mask[j]);
+  }
+  last = -1;
+#pragma unroll
+  for (int j = 16; j >= 0; --j) {
+    above[j] = last;
+    if (mask[j]) last = 64 * j + __ffsll((long long)mask[j]) - 1;
+  }
+
+  const float2* V = a.V + g * PV_BINS;
+  const float2* U = a.U + g * PV_BINS;
+#pragma unroll
+  for (int j = 0; j < 17; ++j) {
+    const int b = 64 * j + lane;
+    if (b >= PV_BINS) continue;
+    const unsigned long long lo = mask[j] & (~0ull >> (63 - lane)), hi = mask[j] & (~0ull << lane);
+    const int p = lo ? 64 * j + 63 - __clzll((long long)lo) : below[j];
+    const int q = hi ? 64 * j + __ffsll((long long)hi) - 1 : above[j];
+    const int o = p < 0 ? q : (q < 0 ? p : (b <= ((p + q) >> 1) ? p : q));  // a peak: p == q == b
+    a.owner[g * PV_BINS + b] = (uint16_t)o;
+    float2 M = V[b];
+    if (!reset && o != b) {
+      const float2 vo = V[o], uo = U[o], ub = U[b];
+      const double2 r = pv_mul64(make_double2((double)ub.x, (double)ub.y), make_double2((double)uo.x, -(double)uo.y));
+      const double2 z = pv_mul64(make_double2((double)vo.x, (double)vo.y), r);
+      M = make_float2((float)z.x, (float)z.y);
+    }
+    a.M[g * PV_BINS + b] = M;
+  }
+}
+
+// grid (tiles, files); MODE 0: tile aggregates, MODE 1: apply from the carries
+template <int MODE>
+__global__ __launch_bounds__(256) void pv_lock_tile_kernel(PvLockArgs a) {
+  const Span span_(a.span);
+  __shared__ double2 sp[2][PV_LROW];
+  __shared__ uint16_t ss[2][PV_LROW];
+  const int t = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
+  const int64_t fb = a.frame_base[f], K = a.frame_base[f + 1] - fb;
+  const int64_t k0 = (int64_t)t * PV_TILE;
+  if (k0 >= K) return;  // the whole workgroup
+  const int64_t k1 = min(K, k0 + PV_TILE);
+  const int64_t row = pv_row0(fb, f) + t;
+#pragma unroll
+  for (int i = 0; i < PV_LBPT; ++i) {
+    const int b = tid + 256 * i;
+    if (b < PV_BINS) {
+      sp[0][b] = MODE ? a.carry[row * PV_BINS + b] : make_double2(1.0, 0.0);
+      ss[0][b] = (uint16_t)b;
+    }
+  }
+  float2 Mn[PV_LBPT];
+  unsigned on[PV_LBPT];
+  // loads without a branch around them (lanes past the row and the step past the tile read a
+  // clamped address again): a guarded load makes the compiler drain every load at the join
+  auto fetch = [&](int64_t k) {
+    k = min(k, k1 - 1);
+#pragma unroll
+    for (int i = 0; i < PV_LBPT; ++i) {
+      const int b = min(tid + 256 * i, PV_BINS - 1);
+      Mn[i] = a.M[(fb + k) * PV_BINS + b];
+      on[i] = a.owner[(fb + k) * PV_BINS + b];
+    }
+  };
+  fetch(k0);
+  __syncthreads();
+  int cur = 0;
+  for (int64_t k = k0; k < k1; ++k) {
+    const bool reset = k == 0 || a.empty[fb + k - 1] != 0;
+    float2 Mc[PV_LBPT];
+    unsigned oc[PV_LBPT];
+#pragma unroll
+    for (int i = 0; i < PV_LBPT; ++i) {
+      Mc[i] = Mn[i];
+      oc[i] = on[i];
+    }
+    fetch(k + 1);
+#pragma unroll
+    for (int i = 0; i < PV_LBPT; ++i) {
+      const int b = tid + 256 * i;
+      if (b >= PV_BINS) continue;
+      const int o = min(oc[i], (unsigned)(PV_BINS - 1));
+      double2 p;
+      unsigned s;
+      if (reset) {
+        p = make_double2((double)Mc[i].x, (double)Mc[i].y);
+        s = PV_ABS;
+      } else {
+        p = pv_mul(sp[cur][o], Mc[i]);
+        s = ss[cur][o];
+      }
+      sp[cur ^ 1][b] = p;
+      ss[cur ^ 1][b] = (uint16_t)s;
+      if (MODE) {
+        float2 out = Mc[i];  // a reset frame: V itself
+        if (!reset) {
+          const double2 q = pv_ph64(p);
+          out = make_float2((float)q.x, (float)q.y);
+        }
+        a.phi[(fb + k) * PV_BINS + b] = out;
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  if (!MODE) {
+#pragma unroll
+    for (int i = 0; i < PV_LBPT; ++i) {
+      const int b = tid + 256 * i;
+      if (b < PV_BINS) {
+        a.agg[row * PV_BINS + b] = sp[cur][b];
+        a.asrc[row * PV_BINS + b] = ss[cur][b];
+      }
+    }
+  }
+}
+
+// grid (files): Phi of the frame before each tile, tile after tile, by the aggregates' gather
+__global__ __launch_bounds__(256) void pv_lock_carry_kernel(PvLockArgs a) {
+  const Span span_(a.span);
+  __shared__ double2 sc[2][PV_LROW];
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const int64_t fb = a.frame_base[f], K = a.frame_base[f + 1] - fb;
+  const int64_t tiles = (K + PV_TILE - 1) / PV_TILE, row0 = pv_row0(fb, f);
+  if (tiles <= 0) return;
+#pragma unroll
+  for (int i = 0; i < PV_LBPT; ++i) {
+    const int b = tid + 256 * i;
+    if (b < PV_BINS) sc[0][b] = make_double2(1.0, 0.0);
+  }
+  // the aggregates do not depend on the chain: PV_CDEPTH tiles are in flight ahead of the walk
+  double2 gq[PV_CDEPTH][PV_LBPT];
+  unsigned sq[PV_CDEPTH][PV_LBPT];
+  // (loads without a branch around them, as in the tile pass: clamped, re-reading the last tile)
+  auto fetch = [&](int d, int64_t t) {
+    t = min(t, tiles - 1);
+#pragma unroll
+    for (int i = 0; i < PV_LBPT; ++i) {
+      const int b = min(tid + 256 * i, PV_BINS - 1);
+      gq[d][i] = a.agg[(row0 + t) * PV_BINS + b];
+      sq[d][i] = a.asrc[(row0 + t) * PV_BINS + b];
+    }
+  };
+#pragma unroll
+  for (int d = 0; d < PV_CDEPTH; ++d) fetch(d, d);
+  __syncthreads();
+  int cur = 0;
+  for (int64_t t0 = 0; t0 < tiles; t0 += PV_CDEPTH) {
+#pragma unroll
+    for (int d = 0; d < PV_CDEPTH; ++d) {
+      const int64_t t = t0 + d;
+      if (t >= tiles) break;  // the whole workgroup
+      double2 gc[PV_LBPT];
+      unsigned scur[PV_LBPT];
+#pragma unroll
+      for (int i = 0; i < PV_LBPT; ++i) {
+        gc[i] = gq[d][i];
+        scur[i] = sq[d][i];
+      }
+      fetch(d, t + PV_CDEPTH);
+#pragma unroll
+      for (int i = 0; i < PV_LBPT; ++i) {
+        const int b = tid + 256 * i;
+        if (b >= PV_BINS) continue;
+        a.carry[(row0 + t) * PV_BINS + b] = sc[cur][b];
+        const bool abs_ = scur[i] >= (unsigned)PV_BINS;
+        const double2 c = sc[cur][abs_ ? 0 : scur[i]];
+        double2 n = abs_ ? gc[i] : pv_mul64(c, gc[i]);
+        // a product of unit phasors: renormalised (an f64 square root and two divides, on the one CU
+        // this file has) only once its length has left 1 +- 5e-4 or is not a number; the apply pass
+        // normalises every Phi it stores, and a positive scale does not move a phase
+        const double m2 = n.x * n.x + n.y * n.y;
+        if (!(fabs(m2 - 1.0) < 1e-3)) n = pv_ph64(n);
+        sc[cur ^ 1][b] = n;
+      }
+      __syncthreads();
+      cur ^= 1;
+    }
+  }
+}
+
+int launch_pv_lock(Context& ctx, const float* mag, const float2* U, const float2* V, const uint8_t* empty,
+                   const int64_t* frame_base, int n_files, int64_t total_frames, int64_t max_frames, float2* phi,
+                   uint16_t* owner, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (n_files < 0 || n_files > 65535 || total_frames < 0 || max_frames < 0 || max_frames > total_frames) {
+    set_error("pv_lock: need 0 .. 65535 files and 0 <= max_frames <= total_frames");
+    return -2;
+  }
+  if (n_files == 0 || total_frames == 0) return 0;
+  if (!mag || !U || !V || !empty || !frame_base || !phi || !ws) {
+    set_error("pv_lock: null argument");
+    return -2;
+  }
+  size_t off[5];
+  if (ws_bytes < pv_lock_ws_layout(total_frames, n_files, off)) {
+    set_error("pv_lock: workspace below nc_pv_lock_ws_bytes");
+    return -2;
+  }
+  const int64_t max_tiles = (max_frames + PV_TILE - 1) / PV_TILE;
+  if (max_tiles < 1 || max_tiles > 0x7fffffff || ((uintptr_t)ws & 15) || (total_frames + 3) / 4 > 0x7fffffff) {
+    set_error("pv_lock: max_frames must be the longest file's frame count (at least 1), ws 16-byte aligned");
+    return -2;
+  }
+  char* w = static_cast<char*>(ws);
+  PvLockArgs a{mag, U, V, empty, frame_base, n_files, total_frames,
+               owner ? owner : reinterpret_cast<uint16_t*>(w + off[1]), reinterpret_cast<float2*>(w + off[0]), phi,
+               reinterpret_cast<double2*>(w + off[2]), reinterpret_cast<uint16_t*>(w + off[4]),
+               reinterpret_cast<double2*>(w + off[3]), nullptr};
+  const dim3 gt((unsigned)max_tiles, (unsigned)n_files);
+  {
+    KTimer kt_(ctx, "pv_lock_prep", st);
+    a.span = kt_.span();
+    hipLaunchKernelGGL(pv_lock_prep_kernel, dim3((unsigned)((total_frames + 3) / 4)), dim3(256), 0, st, a);
+  }
+  {
+    KTimer kt_(ctx, "pv_lock_tile", st);
+    a.span = kt_.span();
+    hipLaunchKernelGGL(pv_lock_tile_kernel<0>, gt, dim3(256), 0, st, a);
+  }
+  {
+    KTimer kt_(ctx, "pv_lock_carry", st);
+    a.span = kt_.span();
+    hipLaunchKernelGGL(pv_lock_carry_kernel, dim3((unsigned)n_files), dim3(256), 0, st, a);
+  }
+  {
+    KTimer kt_(ctx, "pv_lock_apply", st);
+    a.span = kt_.span();
+    hipLaunchKernelGGL(pv_lock_tile_kernel<1>, gt, dim3(256), 0, st, a);
+  }
+  NC_HIP(hipGetLastError());
+  return 0;
+}
+
+// m[i] = ((x_0[i] + x_1[i]) + ...) in float32, channel order; grid (blocks, groups)
+__global__ __launch_bounds__(256) void pv_mid_sum_kernel(const float* __restrict__ x,
+                                                         const int64_t* __restrict__ sig_off,
+                                                         const int64_t* __restrict__ sig_len,
+                                                         const int* __restrict__ group_first, float* __restrict__ mid,
+                                                         const int64_t* __restrict__ mid_off,
+                                                         unsigned long long* span) {
+  const Span span_(span);
+  const int gr = blockIdx.y, c0 = group_first[gr], c1 = group_first[gr + 1];
+  if (c1 <= c0) return;
+  int64_t n = sig_len[c0];
+  for (int c = c0 + 1; c < c1; ++c) n = min(n, sig_len[c]);  // equal by contract (checked on the host)
+  float* out = mid + mid_off[gr];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float acc = x[sig_off[c0] + i];
+    for (int c = c0 + 1; c < c1; ++c) acc = __fadd_rn(acc, x[sig_off[c] + i]);
+    out[i] = acc;
+  }
+}
+
+int launch_pv_mid_sum(Context& ctx, const float* x, const int64_t* sig_off, const int64_t* sig_len,
+                      const int* group_first, const int64_t* host_len, const int* host_first, int n_groups,
+                      float* mid, const int64_t* mid_off, hipStream_t st) {
+  if (n_groups < 0 || n_groups > 65535) {
+    set_error("pv_mid_sum: need 0 .. 65535 groups");
+    return -2;
+  }
+  if (n_groups == 0) return 0;
+  if (!host_len || !host_first) {
+    set_error("pv_mid_sum: null host lengths");
+    return -2;
+  }
+  int64_t max_len = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    if (host_first[g] < 0 || host_first[g + 1] <= host_first[g]) {
+      set_error("pv_mid_sum: group_first must rise by at least one channel per group");
+      return -2;
+    }
+    const int64_t n = host_len[host_first[g]];
+    for (int c = host_first[g]; c < host_first[g + 1]; ++c)
+      if (host_len[c] != n || n < 0) {
+        set_error("pv_mid_sum: the channels of a group must be equally long");
+        return -2;
+      }
+    max_len = std::max(max_len, n);
+  }
+  if (max_len == 0) return 0;
+  if (!x || !sig_off || !sig_len || !group_first || !mid || !mid_off) {
+    set_error("pv_mid_sum: null argument");
+    return -2;
+  }
+  const unsigned bx = (unsigned)std::min<int64_t>((max_len + 1023) / 1024, 4096);
+  {
+    KTimer kt_(ctx, "pv_mid_sum", st);
+    hipLaunchKernelGGL(pv_mid_sum_kernel, dim3(bx, (unsigned)n_groups), dim3(256), 0, st, x, sig_off, sig_len,
+                       group_first, mid, mid_off, kt_.span());
+  }
+  NC_HIP(hipGetLastError());
+  return 0;
+}
+
+struct PvRotArgs {
+  const float2* psi;    // the groups' locked scans, rows laid out by mid_base
+  const float2* u_mid;
+  const int64_t* mid_base;  // [groups + 1]
+  const float2* u;          // the channels' analysis phasors, rows laid out by frame_base
+  const int64_t* frame_base;  // [files + 1]
+  const int* group_first;     // [groups + 1]
+  int n_files, n_groups;
+  int64_t total_frames;
+  float2* phi;
+  unsigned long long* span;
+};
+
+// one wave per channel frame: Phi^c = ph(Psi U^c conj(U^m)) in f64; a group of one channel copies Psi
+__global__ __launch_bounds__(256) void pv_rotate_kernel(PvRotArgs a) {
+  const Span span_(a.span);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t g = (int64_t)blockIdx.x * 4 + wave;
+  if (g >= a.total_frames) return;
+  const int c = uniform32(seg_of(a.frame_base, a.n_files, g));
+  const int64_t k = g - uniform64(a.frame_base[c]);
+  const int gr = uniform32(seg_of(a.n_groups, (int64_t)c, [&](int m) { return (int64_t)a.group_first[m]; }));
+  const int64_t mb = uniform64(a.mid_base[gr]);
+  if (k >= uniform64(a.mid_base[gr + 1]) - mb) return;  // never, when both plans are nc_pv_plan's
+  const bool single = a.group_first[gr + 1] - a.group_first[gr] == 1;
+  const float2* psi = a.psi + (mb + k) * PV_BINS;
+  const float2* um = a.u_mid + (mb + k) * PV_BINS;
+  const float2* u = a.u + g * PV_BINS;
+  float2* out = a.phi + g * PV_BINS;
+#pragma unroll
+  for (int j = 0; j < 17; ++j) {
+    const int b = 64 * j + lane;
+    if (b >= PV_BINS) continue;
+    float2 r = psi[b];
+    if (!single) {
+      const float2 uc = u[b], m = um[b];
+      const double2 d = pv_mul64(make_double2((double)uc.x, (double)uc.y), make_double2((double)m.x, -(double)m.y));
+      const double2 q = pv_ph64(pv_mul64(make_double2((double)r.x, (double)r.y), d));
+      r = make_float2((float)q.x, (float)q.y);
+    }
+    out[b] = r;
+  }
+}
+
+int launch_pv_rotate(Context& ctx, const float2* psi, const float2* u_mid, const int64_t* mid_base, const float2* u,
+                     const int64_t* frame_base, const int* group_first, int n_files, int n_groups,
+                     int64_t total_frames, float2* phi, hipStream_t st) {
+  if (n_files < 0 || n_files > 65535 || n_groups < 0 || n_groups > n_files || total_frames < 0 ||
+      (total_frames + 3) / 4 > 0x7fffffff) {
+    set_error("pv_rotate: need 0 .. 65535 files, at most as many groups and total_frames >= 0");
+    return -2;
+  }
+  if (n_files == 0 || total_frames == 0) return 0;
+  if (n_groups == 0 || !psi || !u_mid || !mid_base || !u || !frame_base || !group_first || !phi) {
+    set_error("pv_rotate: null argument");
+    return -2;
+  }
+  PvRotArgs a{psi, u_mid, mid_base, u, frame_base, group_first, n_files, n_groups, total_frames, phi, nullptr};
+  {
+    KTimer kt_(ctx, "pv_rotate", st);
+    a.span = kt_.span();
+    hipLaunchKernelGGL(pv_rotate_kernel, dim3((unsigned)((total_frames + 3) / 4)), dim3(256), 0, st, a);
   }
   NC_HIP(hipGetLastError());
   return 0;

@@ -88,6 +88,11 @@ SIGNATURES = {
     "nc_pv_plan": (I32, [I64, P, I32, P, P, P, P, C.POINTER(SZ)]),
     "nc_pv_scan_ws_bytes": (SZ, [I64, I32]),
     "nc_pv_analyze":(I32, [P, P, P, P, P, I32, I64, I64, P, P, P, P]),
+    "nc_pv_analyze_u": (I32, [P, P, P, P, P, I32, I64, I64, P, P, P, P, P]),
+    "nc_pv_lock_ws_bytes": (SZ, [I64, I32]),
+    "nc_pv_lock": (I32, [P, P, P, P, P, P, I32, I64, I64, P, P, P, SZ, P]),
+    "nc_pv_mid_sum": (I32, [P, P, P, P, P, P, P, I32, P, P, P]),
+    "nc_pv_rotate": (I32, [P, P, P, P, P, P, P, I32, I32, I64, P, P]),
     "nc_pv_scan": (I32, [P, P, P, P, I32, I64, I64, P, P, SZ, P]),
     "nc_pv_synth": (I32, [P, P, P, P, P, I32, I64, I64, I64, P, SZ, P, P, P, P]),
     "nc_pv_stretch": (I32, [P, P, P, P, P, I32, I64, I64, I64, I64, P, P, P, P, P, SZ, P]),

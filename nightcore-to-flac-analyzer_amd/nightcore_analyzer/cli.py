@@ -52,14 +52,19 @@ def _build_parser() -> argparse.ArgumentParser:
                         "to this file on the GPU: WAV, or FLAC when the name ends in .flac")
     p.add_argument("--semitones", type=float, default=None, metavar="S",
                    help="With --pitch-correct: the shift in semitones (-12 .. 12)")
+    p.add_argument("--phase-lock", action="store_true",
+                   help="With --pitch-correct: identity phase locking, the file's channels linked to the phases "
+                        "of their sum (keeps the level of sustained sounds and the stereo image)")
     return p
 
 
 def _pitch_correct(args, src_path: Path, log) -> None:
     from . import render
-    info = render.pitch_file(src_path, args.pitch_correct, args.semitones, limit_db=args.limit)
+    info = render.pitch_file(src_path, args.pitch_correct, args.semitones, limit_db=args.limit,
+                             phase_lock=bool(args.phase_lock))
     if log is not None:
-        log(f"\nPitch-corrected file written to: {info.path}  (pitch {info.semitones:+.6f} st, ratio "
+        lock = ", phase-locked" if info.phase_lock else ""
+        log(f"\nPitch-corrected file written to: {info.path}  (pitch {info.semitones:+.6f} st{lock}, ratio "
             f"{info.factor:.6f}, peak {info.peak_dbfs:+.2f} dBFS, {info.clipped_samples} clipped samples)")
         if info.limit_db is not None:
             log(f"Limiter at {info.limit_db:+.2f} dBFS: true peak {render._dbfs(info.true_peak):+.2f} dBFS before, "
@@ -120,6 +125,8 @@ def main(argv: list[str] | None = None) -> int:
         errors.append("--pitch-correct needs --semitones")
     if args.semitones is not None and not args.pitch_correct:
         errors.append("--semitones needs --pitch-correct")
+    if args.phase_lock and not args.pitch_correct:
+        errors.append("--phase-lock needs --pitch-correct")
     if args.semitones is not None and not abs(args.semitones) <= 12.0:
         errors.append("--semitones must be within -12 .. 12")
     if args.limit is not None and not args.limit <= 0.0:

@@ -824,6 +824,10 @@ class Engine:
     LIMITER_TAGS = ("limiter_peak", "limiter_gain", "limiter_carry", "limiter_apply")
     # the phase-vocoder stretch's six launches (pvoc.hip), read on request: kernel_times(PV_TAGS)
     PV_TAGS = ("pv_analysis", "pv_scan_tile", "pv_scan_carry", "pv_scan_apply", "pv_synth", "pv_ola")
+    # the phase-locked stretch's launches (ops.pv_stretch_device(lock="identity")): 7 unlinked, 10 linked
+    # (pv_analysis runs twice there, pv_mid_sum and pv_rotate once each)
+    PV_LOCK_TAGS = ("pv_mid_sum", "pv_analysis", "pv_lock_prep", "pv_lock_tile", "pv_lock_carry", "pv_lock_apply",
+                    "pv_rotate", "pv_synth", "pv_ola")
 
     def kernel_profile(self, on) -> None:
         """The library's per-kernel timers (nc_profile_enable): False/0 off, True/1 HIP events

@@ -756,11 +756,9 @@ class PvPlan:
         self.max_ns = int(self.ns.max()) if n else 0
 
 
-def pv_analyze_device(eng: Engine, src, P: int):
-    """Stage 1 alone (``nc_pv_analyze``): (mag [frames, 1025] f32, V [frames, 1025, 2] f32,
-    empty [frames] uint8, PvPlan), all on the device."""
-    sig = _signals(eng, src)
-    plan = PvPlan(P, sig.length)
+def _pv_analyze(eng: Engine, sig, plan: "PvPlan", want_u: bool, want_v: bool = True):
+    """(mag, V or None, empty, U or None) of every frame of ``plan``: ``nc_pv_analyze``, or
+    ``nc_pv_analyze_u`` with ``want_u`` (the same kernel body: mag, V and empty are bit-identical)."""
     T = max(1, plan.total_frames)
     up = _Upload()
     up.add("off", sig.off, np.int64)
@@ -768,12 +766,51 @@ def pv_analyze_device(eng: Engine, src, P: int):
     up.add("fb", plan.frame_base, np.int64)
     d = up.commit(eng.dev)
     mag = torch.empty((T, PV_BINS), dtype=torch.float32, device=eng.dev)
-    v = torch.empty((T, PV_BINS, 2), dtype=torch.float32, device=eng.dev)
+    v = torch.empty((T, PV_BINS, 2), dtype=torch.float32, device=eng.dev) if want_v else None
     empty = torch.empty(T, dtype=torch.uint8, device=eng.dev)
-    eng.call("nc_pv_analyze", sig.buf.data_ptr(), d["off"].data_ptr(), d["len"].data_ptr(), d["fb"].data_ptr(),
-             plan.n_files, plan.total_frames, plan.P, mag.data_ptr(), v.data_ptr(), empty.data_ptr(), eng.stream())
+    head = (sig.buf.data_ptr(), d["off"].data_ptr(), d["len"].data_ptr(), d["fb"].data_ptr(), plan.n_files,
+            plan.total_frames, plan.P, mag.data_ptr(), v.data_ptr() if want_v else 0, empty.data_ptr())
     t = plan.total_frames
-    return mag[:t], v[:t], empty[:t], plan
+    if not want_u:
+        eng.call("nc_pv_analyze", *head, eng.stream())
+        return mag[:t], v[:t], empty[:t], None
+    u = torch.empty((T, PV_BINS, 2), dtype=torch.float32, device=eng.dev)
+    eng.call("nc_pv_analyze_u", *head, u.data_ptr(), eng.stream())
+    return mag[:t], (v[:t] if want_v else None), empty[:t], u[:t]
+
+
+def pv_analyze_device(eng: Engine, src, P: int, phasors: bool = False):
+    """Stage 1 alone (``nc_pv_analyze``): (mag [frames, 1025] f32, V [frames, 1025, 2] f32,
+    empty [frames] uint8, PvPlan), all on the device.  ``phasors``: the analysis phasors
+    U = ph(A) [frames, 1025, 2] f32 as a fifth value (``nc_pv_analyze_u``; the first three are
+    bit-identical)."""
+    sig = _signals(eng, src)
+    plan = PvPlan(P, sig.length)
+    mag, v, empty, u = _pv_analyze(eng, sig, plan, bool(phasors))
+    return (mag, v, empty, plan, u) if phasors else (mag, v, empty, plan)
+
+
+def pv_lock_device(eng: Engine, mag: torch.Tensor, u: torch.Tensor, v: torch.Tensor, empty: torch.Tensor,
+                   frame_base: Sequence[int]):
+    """The phase-locked scan alone (``nc_pv_lock``; DESIGN.md §4 "Phase locking"): (Phi
+    [frames, 1025, 2] f32, owner [frames, 1025] uint16 — viewed as int16 storage) from the
+    magnitudes, analysis phasors U, V and empty flags of files whose frames start at
+    ``frame_base`` [files + 1].  Four launches, no host synchronisation."""
+    fb = np.ascontiguousarray(frame_base, np.int64).reshape(-1)
+    n, total = len(fb) - 1, int(fb[-1])
+    mag, u, v, empty = mag.contiguous(), u.contiguous(), v.contiguous(), empty.contiguous()
+    if (tuple(mag.shape) != (total, PV_BINS) or tuple(u.shape) != (total, PV_BINS, 2) or
+            tuple(v.shape) != (total, PV_BINS, 2) or tuple(empty.shape) != (total,)):
+        raise ValueError("mag / U / V / empty do not match frame_base")
+    phi = torch.empty_like(v)
+    owner = torch.zeros((total, PV_BINS), dtype=torch.int16, device=eng.dev)
+    if total == 0:
+        return phi, owner
+    ws = eng.workspace("pv_lock", int(_native.load().nc_pv_lock_ws_bytes(total, n)))
+    d = h2d(fb, np.int64, eng.dev)
+    eng.call("nc_pv_lock", mag.data_ptr(), u.data_ptr(), v.data_ptr(), empty.data_ptr(), d.data_ptr(), n, total,
+             int(np.diff(fb).max()), phi.data_ptr(), owner.data_ptr(), ws.data_ptr(), ws.numel(), eng.stream())
+    return phi, owner
 
 
 def pv_scan_device(eng: Engine, v: torch.Tensor, empty: torch.Tensor, frame_base: Sequence[int]) -> torch.Tensor:
@@ -820,11 +857,65 @@ def pv_synth_device(eng: Engine, mag: torch.Tensor, phi: torch.Tensor, lengths: 
     return DeviceSignals(s, o_off, plan.ns.copy()), peak[:n]
 
 
-def pv_stretch_device(eng: Engine, src, P: int):
+PV_LOCKS = (None, "identity")
+
+
+def _pv_stretch_locked(eng: Engine, src, P: int, channels):
+    """The locked stretch: every group of ``channels`` consecutive signals follows one locked scan
+    (its own for a single channel, that of the channels' float32 sum otherwise)."""
+    sig, first, lens = _limiter_files(eng, src, channels)
+    counts = np.diff(first)
+    for g in range(len(counts)):
+        if np.any(lens[first[g]:first[g + 1]] != lens[first[g]]):
+            raise ValueError("the channels of a linked group must be equally long")
+    plan = PvPlan(P, lens)
+    if plan.n_files == 0 or np.all(counts == 1):
+        mag, v, empty, u = _pv_analyze(eng, sig, plan, True)
+        phi, _ = pv_lock_device(eng, mag, u, v, empty, plan.frame_base)
+    else:
+        n_groups = len(counts)
+        m_len = np.ascontiguousarray(lens[first[:-1]], np.int64)
+        m_off, m_total = _packed(m_len)
+        up = _Upload()
+        up.add("off", sig.off, np.int64)
+        up.add("len", lens, np.int64)
+        up.add("first", first, np.int32)
+        up.add("m_off", m_off, np.int64)
+        d = up.commit(eng.dev)
+        mid = DeviceSignals(torch.zeros(max(_ALIGN, m_total), dtype=torch.float32, device=eng.dev), m_off, m_len)
+        eng.call("nc_pv_mid_sum", sig.buf.data_ptr(), d["off"].data_ptr(), d["len"].data_ptr(), d["first"].data_ptr(),
+                 lens.ctypes.data, first.ctypes.data, n_groups, mid.buf.data_ptr(), d["m_off"].data_ptr(),
+                 eng.stream())
+        m_plan = PvPlan(P, m_len)
+        m_mag, m_v, m_empty, m_u = _pv_analyze(eng, mid, m_plan, True)
+        psi, _ = pv_lock_device(eng, m_mag, m_u, m_v, m_empty, m_plan.frame_base)
+        mag, _, _, u = _pv_analyze(eng, sig, plan, True, want_v=False)
+        phi = torch.empty_like(u)
+        up = _Upload()
+        up.add("fb", plan.frame_base, np.int64)
+        up.add("m_fb", m_plan.frame_base, np.int64)
+        up.add("first", first, np.int32)
+        d = up.commit(eng.dev)
+        if plan.total_frames:
+            eng.call("nc_pv_rotate", psi.data_ptr(), m_u.data_ptr(), d["m_fb"].data_ptr(), u.data_ptr(),
+                     d["fb"].data_ptr(), d["first"].data_ptr(), plan.n_files, n_groups, plan.total_frames,
+                     phi.data_ptr(), eng.stream())
+    out, peak = pv_synth_device(eng, mag, phi, lens, P)
+    return out, peak, plan
+
+
+def pv_stretch_device(eng: Engine, src, P: int, lock: Optional[str] = None, channels=1):
     """Every file of ``src`` (arrays, or ``DeviceSignals`` already in HBM) stretched in time by
     P / 10^6 with its pitch kept (the phase vocoder of DESIGN.md §4 "Pitch shift";
     ``nc_pv_stretch``, six launches), the result left in HBM: (DeviceSignals of the stretched
-    signals, device float32 peak[file] = max |s|, PvPlan).  No host synchronisation."""
+    signals, device float32 peak[file] = max |s|, PvPlan).  No host synchronisation.
+    ``lock="identity"``: identity phase locking (DESIGN.md §4 "Phase locking"), with every group of
+    ``channels`` consecutive, equally long signals (an int, or one count per group, as for the
+    limiter) linked to the phases of its sum; 7 launches unlinked, 10 linked."""
+    if lock not in PV_LOCKS:
+        raise ValueError(f"lock must be one of {PV_LOCKS!r}")
+    if lock is not None:
+        return _pv_stretch_locked(eng, src, P, channels)
     sig = _signals(eng, src)
     plan = PvPlan(P, sig.length)
     n = plan.n_files
@@ -845,21 +936,26 @@ def pv_stretch_device(eng: Engine, src, P: int):
     return DeviceSignals(s, o_off, plan.ns.copy()), peak[:n], plan
 
 
-def pitch_shift_device(eng: Engine, src, semitones: float):
+def pitch_shift_device(eng: Engine, src, semitones: float, lock: Optional[str] = None, channels=1):
     """Every file of ``src`` (arrays, or ``DeviceSignals`` already in HBM) shifted in pitch by
-    ``semitones`` with its duration kept: the stretch by P / 10^6 (``pv_stretch_device``), then
-    the speed render at the same ratio (``speed_render_device``), cut to the input's length.
+    ``semitones`` with its duration kept: the stretch by P / 10^6 (``pv_stretch_device``, with its
+    ``lock`` and ``channels``), then the speed render at the same ratio (``speed_render_device``),
+    cut to the input's length.
     Returns (DeviceSignals of length n per file, device float32 peak[file] of the render, P).
     The peak is that of the whole render, ceil(Ns 10^6 / P) >= n samples.  No host
     synchronisation."""
+    if lock not in PV_LOCKS:
+        raise ValueError(f"lock must be one of {PV_LOCKS!r}")
     sig = _signals(eng, src)
     P = pitch_p(semitones)
-    stretched, _, _ = pv_stretch_device(eng, sig, P)
+    stretched, _, _ = pv_stretch_device(eng, sig, P, lock=lock, channels=channels)
     out, peak, _ = speed_render_device(eng, stretched, P / PV_Q)
     return DeviceSignals(out.buf, out.off, np.asarray(sig.length, np.int64).copy()), peak, P
 
 
-def pitch_shift(eng: Engine, arrays: Sequence[np.ndarray], semitones: float) -> List[np.ndarray]:
+def pitch_shift(eng: Engine, arrays: Sequence[np.ndarray], semitones: float, lock: Optional[str] = None,
+                channels=1) -> List[np.ndarray]:
     """Each array shifted by ``semitones`` (float32, the input's length)."""
-    out, _, _ = pitch_shift_device(eng, [np.asarray(a, np.float32) for a in arrays], semitones)
+    out, _, _ = pitch_shift_device(eng, [np.asarray(a, np.float32) for a in arrays], semitones, lock=lock,
+                                   channels=channels)
     return _read_back(out.buf, out.off, out.length)

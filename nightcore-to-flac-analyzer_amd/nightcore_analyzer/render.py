@@ -218,7 +218,9 @@ def refine_speed(nightcore, source, *, start: Optional[float] = None, max_render
 # PARITY UNPINNED: rubberband is not installed and the reference holds no pitch shifter; the
 # definition is this project's own (DESIGN.md §4 "Pitch shift", tests/pvoc_ref.py): a plain
 # phase-vocoder time stretch by 2^(S/12) (no transient detection, no phase locking, channels
-# independent) followed by the speed render at the same ratio.
+# independent) followed by the speed render at the same ratio.  ``phase_lock=True`` opts into
+# identity phase locking with the channels of a file linked to the phases of their sum
+# (DESIGN.md §4 "Phase locking", tests/pvoc_lock_ref.py); transients are still not handled.
 PITCH_TOLERANCE_ST = 0.5   # |shift| below which the reference renders nothing (workflow.py:640, 697)
 
 
@@ -235,13 +237,21 @@ def ps_path(src, version: int) -> Path:
     return src.with_name(f"{src.stem} PS{int(version)}{src.suffix}")
 
 
-def pitch_shift(y: np.ndarray, semitones: float, sr: Optional[int] = None) -> np.ndarray:
+def _lock_mode(phase_lock) -> Optional[str]:
+    if not isinstance(phase_lock, (bool, np.bool_)):
+        raise ValueError(f"phase_lock must be True or False, not {phase_lock!r}")
+    return "identity" if phase_lock else None
+
+
+def pitch_shift(y: np.ndarray, semitones: float, sr: Optional[int] = None, *, phase_lock: bool = False) -> np.ndarray:
     """The mono signal ``y`` shifted in pitch by ``semitones`` (float32, len(y) samples at the same
-    rate).  ``sr`` is accepted for symmetry with the other seams; the shift does not depend on it."""
+    rate).  ``sr`` is accepted for symmetry with the other seams; the shift does not depend on it.
+    ``phase_lock``: identity phase locking (DESIGN.md §4 "Phase locking")."""
     from .engine import get_engine
     from . import ops
     quantize_semitones(semitones)
-    return ops.pitch_shift(get_engine(), [np.asarray(y, np.float32).reshape(-1)], semitones)[0]
+    lock = _lock_mode(phase_lock)
+    return ops.pitch_shift(get_engine(), [np.asarray(y, np.float32).reshape(-1)], semitones, lock=lock)[0]
 
 
 @dataclass
@@ -250,24 +260,28 @@ class PitchInfo(RenderInfo):
     and whose ``peak`` is that of the whole render (up to two samples longer than the file) when
     no limiter ran."""
     semitones: float = 0.0     # the shift applied (six decimals)
+    phase_lock: bool = False   # identity phase locking, the file's channels linked
 
 
 def pitch_file(src_path, dst_path, semitones: float, limit_db: Optional[float] = None, *,
-               attack_ms: float = 5.0, release_ms: float = 50.0) -> PitchInfo:
+               attack_ms: float = 5.0, release_ms: float = 50.0, phase_lock: bool = False) -> PitchInfo:
     """Shift every channel of the WAV or FLAC file ``src_path`` by ``semitones`` at its own rate and
     write ``dst_path`` (same rate, channels and length): a 16-bit PCM source gives a 16-bit PCM
     file (``nc_f32_to_pcm16``), anything else a float32 file; a ``.flac`` destination is encoded on
     the device as in ``speed_file``.  With a ceiling ``limit_db`` the
-    true-peak limiter runs on the resident result first, as in ``speed_file``."""
+    true-peak limiter runs on the resident result first, as in ``speed_file``.  ``phase_lock``:
+    identity phase locking with all channels of the file linked to the phases of their sum
+    (DESIGN.md §4 "Phase locking")."""
     from .engine import get_engine
     from .ops import f32_to_pcm16_device, limiter_windows, pitch_shift_device, true_peak_limit_device
     ratio = quantize_semitones(semitones)
+    lock = _lock_mode(phase_lock)
     if limit_db is not None and not float(limit_db) <= 0.0:
         raise ValueError(f"limiter ceiling {limit_db!r} dBFS is above full scale")
     data, sr, fmt = read_audio_channels(src_path)
     eng = get_engine()
-    out, peak_d, P = pitch_shift_device(eng, list(data), semitones)
     ch, n_out = data.shape[0], int(data.shape[1])
+    out, peak_d, P = pitch_shift_device(eng, list(data), semitones, lock=lock, channels=max(1, ch))
     extra = {}
     if limit_db is not None and ch:
         wa, wr = limiter_windows(sr, attack_ms, release_ms)
@@ -293,7 +307,7 @@ def pitch_file(src_path, dst_path, semitones: float, limit_db: Optional[float] =
         extra.update(true_peak=float(extra["true_peak"][0].item()),
                      limited_samples=int(extra["limited_samples"][0].item()))
     return PitchInfo(Path(dst_path), ratio, n_out, ch, sr, out_fmt, peak, _dbfs(peak), clipped,
-                     semitones=round(float(semitones), 6), **extra)
+                     semitones=round(float(semitones), 6), phase_lock=lock is not None, **extra)
 
 
 @dataclass
@@ -328,14 +342,14 @@ def _pitch_shift_estimate(cur, nc, sr: int, log):
 
 
 def refine_pitch(nightcore, source, *, start: Optional[float] = None, max_renders: int = 4,
-                 log: Optional[Callable[[str], None]] = None) -> PitchRefinement:
+                 log: Optional[Callable[[str], None]] = None, phase_lock: bool = False) -> PitchRefinement:
     """The workflow's pitch-correction loop (workflow.py:652-704) without its prompts, on the
     22 050 Hz mono analysis copies.  First shift: ``start``, else
     12 log2(median nc_hz / median src_hz) of ``pitch.estimate_pitch_combined``; below 0.5 st
     nothing is rendered (converged, no shifts).  Each pass shifts the CURRENT render (the source
     at first) by the shift on the device, re-estimates the nightcore against it and makes the
     residual the next shift; it stops when the residual is below 0.5 st.  The render stays in
-    HBM between the passes.
+    HBM between the passes.  ``phase_lock``: every render uses identity phase locking.
 
     The chroma estimate keeps the reference's ``lag / 3`` (pitch.py: 36 bins per octave folded to
     12 chroma bins), so without MELODIA a true shift of S semitones is reported as
@@ -350,6 +364,7 @@ def refine_pitch(nightcore, source, *, start: Optional[float] = None, max_render
 
     if max_renders < 1:
         raise ValueError("refine_pitch: max_renders must be at least 1")
+    lock = _lock_mode(phase_lock)
     nc = as_f32(pipeline._load(nightcore, _log, "nightcore"))
     src = as_f32(pipeline._load(source, _log, "source"))
     out = PitchRefinement()
@@ -370,7 +385,7 @@ def refine_pitch(nightcore, source, *, start: Optional[float] = None, max_render
     host_estimate = pitch.melodia_backend() is not None   # MELODIA reads host arrays
     for k in range(max_renders):
         _log(f"Render {k + 1}: pitch {shift:+.6f} st")
-        resident, _, _ = pitch_shift_device(eng, resident, shift)
+        resident, _, _ = pitch_shift_device(eng, resident, shift, lock=lock)
         out.render = DeviceAudio(resident.buf[:int(resident.length[0])])
         out.shifts.append(round(float(shift), 6))
         cur = out.render.numpy() if host_estimate else out.render
