@@ -36,6 +36,7 @@ constexpr int SF_BINS = 1025;
 constexpr int SF_ROW = 1028;  // dB row stride (floats): 16-byte aligned rows
 constexpr int SF_REC = 8;     // per-frame record: centroid, rolloff Hz, 5 band sums, max |X|
 constexpr int SF_NBANDS = 5;
+constexpr float SF_DB_FLOOR = -100.0f;  // 10 log10(1e-10): amplitude_to_db's amin^2
 using SfTw = StagedTw<1024>;
 
 struct SpecArgs {
@@ -145,7 +146,9 @@ __global__ __launch_bounds__(SF_THREADS) void spectral_frames_kernel(SpecArgs a)
     // 9 % slower: 5.19 against 4.78 ms per 128 files)
     auto bin = [&](int k) {
       const float s = mag[k];
-      row[k] = db10_floor(s * s);  // = 10 log10f(max(1e-10, s^2)), bit for bit
+      // 10 log10f(max(1e-10, s^2)); the device log10f puts the floor itself one ulp below -100
+      // (-100.00001), power_to_db's f32 floor is -100.0 exactly: the maximum restores it
+      row[k] = fmaxf(db10_floor(s * s), SF_DB_FLOOR);
       l1 += (double)s;
       m1 = fma((double)k, (double)s, m1);
       mx = fmaxf(mx, s);
@@ -325,7 +328,7 @@ __global__ __launch_bounds__(SB_NT) void spectral_bins_kernel(const int64_t* fra
   if (t0 >= t1) return;
   // amplitude_to_db -> power_to_db(|S|^2, ref=max|S|^2, amin=1e-10): the f32 reference level
   const float ref = (float)stats[f * 12 + 7];
-  const float rdb = 10.0f * log10f(fmaxf(1e-10f, ref * ref));
+  const float rdb = fmaxf(10.0f * log10f(fmaxf(1e-10f, ref * ref)), SF_DB_FLOOR);  // the rows' floor: 0 dB on silence
   const int x = threadIdx.x;
   double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
   auto add = [&](float4 v) {
