@@ -35,7 +35,7 @@ extern "C" {
 
 typedef struct nc_ctx nc_ctx;
 
-#define NCGPU_ABI_VERSION 5  /* 5: nc_pcm16_to_f32; 4: nc_melodia_salience; 3: tuning decision margins, nc_xcorr_peak */
+#define NCGPU_ABI_VERSION 6  /* 6: nc_melodia_probe; 5: nc_pcm16_to_f32; 4: nc_melodia_salience; 3: tuning decision margins, nc_xcorr_peak */
 
 int nc_abi_version(void);
 const char* nc_last_error(void);
@@ -671,6 +671,21 @@ int nc_melodia_salience(nc_ctx* ctx, const float* sig, const int64_t* file_off, 
                         const int64_t* frame_base, int n_files, int64_t total_frames, int hop, float sample_rate,
                         const float* win, int sal_min_bin, int* pk_count, int* pk_bin, float* pk_sal,
                         void* stream);
+/* nc_melodia_probe (ABI 6; for the tests, not on the product path): the same kernel, the same
+ * outputs, and what each stage left, each nullable, device, per frame g:
+ *   dbg_mag  [total_frames][4097] float   |X[k]|, k = 0..4096
+ *   dbg_npk  [total_frames] int           spectral peaks kept (<= 100)
+ *   dbg_pk_f, dbg_pk_a [total_frames][100] double   their frequency (Hz) and magnitude, in the
+ *            kernel's order (f32 rounding of the magnitude descending, ties by bin); entries
+ *            from dbg_npk[g] on are not written
+ *   dbg_sal  [total_frames][600] double   the salience function
+ * max_blocks: 0 = the grid of nc_melodia_salience (min(total_frames, 2 x CUs)); > 0 caps it, so
+ * that one workgroup walks several frames (results do not depend on it). */
+int nc_melodia_probe(nc_ctx* ctx, const float* sig, const int64_t* file_off, const int64_t* file_len,
+                     const int64_t* frame_base, int n_files, int64_t total_frames, int hop, float sample_rate,
+                     const float* win, int sal_min_bin, int* pk_count, int* pk_bin, float* pk_sal, float* dbg_mag,
+                     int* dbg_npk, double* dbg_pk_f, double* dbg_pk_a, double* dbg_sal, int max_blocks,
+                     void* stream);
 
 /* -------------------------------------------------------------------------
  * FLAC decode — what the reference gets from librosa.load / soundfile for its FLAC

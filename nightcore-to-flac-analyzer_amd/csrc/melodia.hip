@@ -21,6 +21,24 @@
 //      599] with salience > 0, the largest kSalPk by salience (ties: lower bin first).
 // The salience of a bin is summed in a fixed order (contributing harmonic bins ascending, then
 // peak-and-harmonic order), so results are deterministic run to run.
+//
+// Order contract of the two sorts (steps 3 and 5): the interpolated magnitude and the salience are
+// f64, the sort key is their f32 rounding (fkey((float)value)), descending, ties by the lower bin.
+// Two values that differ in f64 but round to the same f32 are therefore ordered by bin, where an
+// f64 sort (the oracle's default) orders them by value; the 100-peak and the kSalPk cut fall on
+// that order.  oracle/melodia_ref.py restates it with key_dtype=np.float32
+// (tests/test_gpu_melodia_stages.py holds the device to it exactly).
+//
+// Degenerate frames: when a file's length is 2 (mod hop) its last frame has one sample under a
+// non-zero window weight (w[0] == 0), and a file of one sample has nothing else.  The spectrum of
+// one sample is flat, so its local maxima, and every salience peak that follows, are rounding
+// noise, in the f64 oracle as much as here; the two need not agree on such a frame and nothing is
+// done about it.  On the last frame of a longer file such peaks are small beside the file's
+// saliences (w[1] = 4.6e-9 against ~1e-3 at the window's centre): below 1e-4 of the largest.
+//
+// nc_melodia_probe launches this same kernel with the dbg_* outputs set (each stage's result,
+// stored at the end of the stage behind a null check) and an optional cap on the grid; the tests
+// use it to check every stage against the oracle applied to the stage before.
 #include <algorithm>
 
 #include "nc_block.h"
@@ -54,6 +72,12 @@ struct MelodiaArgs {
   int* pk_count;              // [total_frames]
   int* pk_bin;                // [total_frames][MD_SALPK]
   float* pk_sal;              // [total_frames][MD_SALPK]
+  // nc_melodia_probe only (null otherwise): the stages' results, per frame
+  float* dbg_mag;             // [total_frames][MD_BINS]   step 2
+  int* dbg_npk;               // [total_frames]            step 3: peaks kept
+  double* dbg_pk_f;           // [total_frames][MD_MAXPK]  step 3, in sorted order (Hz)
+  double* dbg_pk_a;           // [total_frames][MD_MAXPK]
+  double* dbg_sal;            // [total_frames][MD_SAL]    step 4
 };
 
 // ascending bitonic sort of n (a power of two, <= 4 * 1024) keys in LDS by all MD_NT threads
@@ -131,6 +155,7 @@ __global__ __launch_bounds__(MD_NT) void melodia_salience_kernel(MelodiaArgs a) 
       const float2 O = cmul_mi(cscale(csub(za, zb), 0.5f));
       const float2 X = cadd(E, cmul(a.tw[k], O));
       mag[k] = sqrtf(fmaf(X.x, X.x, X.y * X.y));
+      if (a.dbg_mag) a.dbg_mag[g * MD_BINS + k] = mag[k];
     }
     if (tid == 0) ncand = 0;
     __syncthreads();
@@ -157,7 +182,10 @@ __global__ __launch_bounds__(MD_NT) void melodia_salience_kernel(MelodiaArgs a) 
       const double pos = (double)k + 0.5 * ((double)l - r) / ((double)l - 2.0 * c + r);
       pk_a[tid] = c - 0.25 * ((double)l - r) * (pos - (double)k);
       pk_f[tid] = pos * (double)a.sr / 8192.0;
+      if (a.dbg_pk_f) a.dbg_pk_f[g * MD_MAXPK + tid] = pk_f[tid];
+      if (a.dbg_pk_a) a.dbg_pk_a[g * MD_MAXPK + tid] = pk_a[tid];
     }
+    if (tid == 0 && a.dbg_npk) a.dbg_npk[g] = np;
     for (int b = tid; b <= MD_BUCKETS; b += MD_NT) bcount[b] = 0;
     __syncthreads();
     // 4. salience entries of the peaks within 40 dB of the largest (MD_NH harmonics each, stopping
@@ -218,6 +246,7 @@ __global__ __launch_bounds__(MD_NT) void melodia_salience_kernel(MelodiaArgs a) 
         for (int i = bstart[hb]; i < bstart[hb + 1]; ++i) s += ent_w[ent_pos[i]] * nbw;
       }
       sal[b] = s;
+      if (a.dbg_sal) a.dbg_sal[g * MD_SAL + b] = s;
     }
     if (tid == 0) npk = 0;
     __syncthreads();
@@ -250,10 +279,11 @@ __global__ __launch_bounds__(MD_NT) void melodia_salience_kernel(MelodiaArgs a) 
 int launch_melodia_salience(Context& ctx, const float* sig, const int64_t* file_off, const int64_t* file_len,
                             const int64_t* frame_base, int n_files, int64_t total_frames, int hop, float sr,
                             const float* win, int sal_min_bin, int* pk_count, int* pk_bin, float* pk_sal,
-                            hipStream_t st) {
+                            float* dbg_mag, int* dbg_npk, double* dbg_pk_f, double* dbg_pk_a, double* dbg_sal,
+                            int max_blocks, hipStream_t st) {
   if (total_frames <= 0 || n_files <= 0) return 0;
-  if (hop <= 0 || sr <= 0.0f || !win) {
-    set_error("melodia_salience: hop and sample rate must be positive, win non-null");
+  if (hop <= 0 || sr <= 0.0f || !win || max_blocks < 0) {
+    set_error("melodia_salience: hop and sample rate must be positive, win non-null, max_blocks >= 0");
     return -2;
   }
   MelodiaArgs a;
@@ -271,7 +301,13 @@ int launch_melodia_salience(Context& ctx, const float* sig, const int64_t* file_
   a.pk_count = pk_count;
   a.pk_bin = pk_bin;
   a.pk_sal = pk_sal;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(total_frames, (int64_t)ctx.num_cu * 2));
+  a.dbg_mag = dbg_mag;
+  a.dbg_npk = dbg_npk;
+  a.dbg_pk_f = dbg_pk_f;
+  a.dbg_pk_a = dbg_pk_a;
+  a.dbg_sal = dbg_sal;
+  int grid = (int)std::max<int64_t>(1, std::min<int64_t>(total_frames, (int64_t)ctx.num_cu * 2));
+  if (max_blocks > 0) grid = std::min(grid, max_blocks);  // the probe: fewer workgroups, more frames each
   {
     KTimer kt_(ctx, "melodia_salience", st);
     hipLaunchKernelGGL(melodia_salience_kernel, dim3(grid), dim3(MD_NT), 0, st, a);

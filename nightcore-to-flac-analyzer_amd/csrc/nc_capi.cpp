@@ -17,7 +17,8 @@ void set_error(const std::string& msg) { g_err = msg; }
 int launch_melodia_salience(Context& ctx, const float* sig, const int64_t* file_off, const int64_t* file_len,
                             const int64_t* frame_base, int n_files, int64_t total_frames, int hop, float sr,
                             const float* win, int sal_min_bin, int* pk_count, int* pk_bin, float* pk_sal,
-                            hipStream_t st);
+                            float* dbg_mag, int* dbg_npk, double* dbg_pk_f, double* dbg_pk_a, double* dbg_sal,
+                            int max_blocks, hipStream_t st);
 struct BeatArgs;
 size_t window_stage_ws_bytes(const Context& ctx, int n_win, int T);
 int launch_window_stage(Context& ctx, const float* sig, const int64_t* win_off, const uint8_t* active,
@@ -846,7 +847,20 @@ int nc_melodia_salience(nc_ctx* ctx, const float* sig, const int64_t* file_off, 
   CHECK_CTX(ctx);
   SET_DEVICE(ctx);
   return nc::launch_melodia_salience(ctx->c, sig, file_off, file_len, frame_base, n_files, total_frames, hop,
-                                     sample_rate, win, sal_min_bin, pk_count, pk_bin, pk_sal, (hipStream_t)stream);
+                                     sample_rate, win, sal_min_bin, pk_count, pk_bin, pk_sal, nullptr, nullptr, nullptr,
+                                     nullptr, nullptr, 0, (hipStream_t)stream);
+}
+
+int nc_melodia_probe(nc_ctx* ctx, const float* sig, const int64_t* file_off, const int64_t* file_len,
+                     const int64_t* frame_base, int n_files, int64_t total_frames, int hop, float sample_rate,
+                     const float* win, int sal_min_bin, int* pk_count, int* pk_bin, float* pk_sal, float* dbg_mag,
+                     int* dbg_npk, double* dbg_pk_f, double* dbg_pk_a, double* dbg_sal, int max_blocks,
+                     void* stream) {
+  CHECK_CTX(ctx);
+  SET_DEVICE(ctx);
+  return nc::launch_melodia_salience(ctx->c, sig, file_off, file_len, frame_base, n_files, total_frames, hop,
+                                     sample_rate, win, sal_min_bin, pk_count, pk_bin, pk_sal, dbg_mag, dbg_npk,
+                                     dbg_pk_f, dbg_pk_a, dbg_sal, max_blocks, (hipStream_t)stream);
 }
 
 }  // extern "C"

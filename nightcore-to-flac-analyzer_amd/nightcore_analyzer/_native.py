@@ -79,6 +79,7 @@ SIGNATURES = {
     "nc_create_rate": (I32, [I32, I32, C.POINTER(P)]),
     "nc_window_energy_blocks": (I32, [P, P, P, I32, P, P, P, I32, I32, P, P]),
     "nc_melodia_salience": (I32, [P, P, P, P, P, I32, I64, I32, F32, P, I32, P, P, P, P]),
+    "nc_melodia_probe": (I32, [P, P, P, P, P, I32, I64, I32, F32, P, I32, P, P, P, P, P, P, P, P, I32, P]),
     "nc_speed_out_len": (I32, [D, P, I32, C.POINTER(I64), P]),
     "nc_speed_render": (I32, [P, P, P, P, I32, I64, P, P, I64, P, P]),
     "nc_f32_to_pcm16": (I32, [P, P, P, P, I32, I64, P, P, I64, P, P]),

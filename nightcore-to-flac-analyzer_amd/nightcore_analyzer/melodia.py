@@ -18,6 +18,14 @@ with the reference's log line).
   (``contours_melody``: PitchContoursMelody: voicing filter, octave-duplicate and pitch-outlier
   removal against a smoothed melody pitch mean, per-frame pick by total salience) on the host:
   sequential decisions over a few hundred contours.
+
+Degenerate frames.  A frame with a single sample under a non-zero window weight has a flat
+spectrum: the last frame of a file whose length is 2 (mod hop) (``window()[0] == 0``), and every
+non-empty frame of a one-sample file.  Its spectral maxima, and the salience peaks built on
+them, are rounding noise, in the f64 oracle as on the device, and the two need not agree there.
+Nothing filters them: on the last frame of a longer file they stay below 1e-4 of the file's
+largest salience (``window()[1]`` is 4.6e-9).  ``salience_probe`` exposes every stage of the
+kernel to the tests (tests/test_gpu_melodia_stages.py).
 """
 from __future__ import annotations
 
@@ -96,6 +104,57 @@ def salience_peaks(eng, arrays: Sequence[np.ndarray], sr: int = 22050, hop: int 
              sal.data_ptr(), eng.stream())
     c, b, s = cnt.cpu().numpy(), bins.cpu().numpy(), sal.cpu().numpy()
     return [SaliencePeaks(c[fb[i]:fb[i + 1]], b[fb[i]:fb[i + 1]], s[fb[i]:fb[i + 1]]) for i in range(len(T))]
+
+
+@dataclass
+class SalienceProbe:
+    """What every stage of the front-end kernel left for one file (nc_melodia_probe): the
+    spectrum mag [T, 4097] f32, the kept spectral peaks npk [T], pk_f / pk_a [T, 100] f64 (row
+    t's first npk[t] entries, in the kernel's order), the salience function sal [T, 600] f64, and
+    the kernel's product output ``peaks``."""
+    mag: np.ndarray
+    npk: np.ndarray
+    pk_f: np.ndarray
+    pk_a: np.ndarray
+    sal: np.ndarray
+    peaks: SaliencePeaks
+
+
+def salience_probe(eng, arrays: Sequence[np.ndarray], sr: int = 22050, hop: int = HOP,
+                   max_blocks: int = 0) -> List[SalienceProbe]:
+    """The tests' view into the front end, never called by the product path: salience_peaks'
+    launch through nc_melodia_probe, which also stores each stage's result.  ``max_blocks`` > 0
+    caps the grid, so that one workgroup walks several frames (0: the product's grid)."""
+    import torch
+    from .engine import _Upload
+    sig = eng.upload_signals([np.asarray(a, np.float32) for a in arrays])
+    T = np.array([n_frames(n, hop) for n in sig.length], np.int64)
+    fb = np.concatenate([[0], np.cumsum(T)]).astype(np.int64)
+    total = int(fb[-1])
+    up = _Upload()
+    up.add("off", sig.off, np.int64)
+    up.add("len", sig.length, np.int64)
+    up.add("fb", fb, np.int64)
+    d = up.commit(eng.dev)
+    win = torch.from_numpy(window()).to(eng.dev)
+    n = max(1, total)
+
+    def z(shape, dtype):
+        return torch.zeros(shape, dtype=dtype, device=eng.dev)
+
+    cnt, bins, sal = z(n, torch.int32), z((n, SALPK), torch.int32), z((n, SALPK), torch.float32)
+    mag, npk = z((n, FFT // 2 + 1), torch.float32), z(n, torch.int32)
+    pk_f, pk_a, fsal = z((n, 100), torch.float64), z((n, 100), torch.float64), z((n, N_BINS), torch.float64)
+    eng.call("nc_melodia_probe", sig.buf.data_ptr(), d["off"].data_ptr(), d["len"].data_ptr(), d["fb"].data_ptr(),
+             len(T), total, hop, float(sr), win.data_ptr(), max(0, cent_bin(MIN_HZ)), cnt.data_ptr(), bins.data_ptr(),
+             sal.data_ptr(), mag.data_ptr(), npk.data_ptr(), pk_f.data_ptr(), pk_a.data_ptr(), fsal.data_ptr(),
+             int(max_blocks), eng.stream())
+    host = [x.cpu().numpy() for x in (mag, npk, pk_f, pk_a, fsal, cnt, bins, sal)]
+    out = []
+    for i in range(len(T)):
+        m, k, f, a, s, c, b, ps = (x[fb[i]:fb[i + 1]] for x in host)
+        out.append(SalienceProbe(m, k, f, a, s, SaliencePeaks(c, b, ps)))
+    return out
 
 
 # ------------------------------------------------------------------------------ contours

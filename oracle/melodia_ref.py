@@ -39,13 +39,16 @@ def frame_mag(y: np.ndarray, t: int, hop: int = HOP, win=None) -> np.ndarray:
     return np.abs(np.fft.rfft(fr * win.astype(np.float64), FFT))
 
 
-def spectral_peaks(mag: np.ndarray, sr: float, max_peaks: int = 100):
+def spectral_peaks(mag: np.ndarray, sr: float, max_peaks: int = 100, key_dtype=np.float64):
+    """The max_peaks largest local maxima, ordered by (key_dtype(value) descending, bin ascending).
+    key_dtype=np.float32 is the device's order contract (csrc/melodia.hip sorts on the f32 rounding
+    of the f64 value); positions and values stay f64 either way."""
     l, c, r = mag[:-2], mag[1:-1], mag[2:]
     k = np.flatnonzero((c > l) & (c >= r) & (c > 0)) + 1
     L, C, R = mag[k - 1], mag[k], mag[k + 1]
     pos = k + 0.5 * (L - R) / (L - 2 * C + R)
     val = C - 0.25 * (L - R) * (pos - k)
-    order = np.lexsort((k, -val))[:max_peaks]
+    order = np.lexsort((k, -val.astype(key_dtype).astype(np.float64)))[:max_peaks]
     return pos[order] * sr / FFT, val[order]
 
 
@@ -72,14 +75,16 @@ def salience(freqs: np.ndarray, mags: np.ndarray) -> np.ndarray:
     return sal
 
 
-def salience_peaks(sal: np.ndarray, min_bin: int, max_out: int = 128):
+def salience_peaks(sal: np.ndarray, min_bin: int, max_out: int = 128, key_dtype=np.float64):
+    """Local maxima of sal in [min_bin, 599] with salience > 0, the max_out largest, ordered by
+    (key_dtype(salience) descending, bin ascending); key_dtype as in spectral_peaks."""
     b = np.arange(max(min_bin, 0), N_BINS)
     c = sal[b]
     left = np.where(b > 0, sal[np.maximum(b - 1, 0)], -np.inf)
     right = np.where(b + 1 < N_BINS, sal[np.minimum(b + 1, N_BINS - 1)], -np.inf)
     m = (c > left) & (c >= right) & (c > 0)
     bb, cc = b[m], c[m]
-    order = np.lexsort((bb, -cc))[:max_out]
+    order = np.lexsort((bb, -cc.astype(key_dtype).astype(np.float64)))[:max_out]
     return bb[order], cc[order]
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import melodia_stage_cases as MC
 from nightcore_analyzer import engine as E
 from nightcore_analyzer import melodia as M
 from nightcore_analyzer import synth
@@ -31,24 +32,30 @@ def test_salience_peaks_match_oracle(eng):
     pk, = M.salience_peaks(eng, [y])
     T = R.n_frames(len(y))
     assert len(pk.counts) == T
-    frames = sorted(set(list(range(0, T, 9)) + [0, 1, T - 2, T - 1]))
-    top_ok = cnt_ok = 0
-    worst = 0.0
+    # every third frame (it was every ninth: with 81 frames a 99 % bar allows no miss at all, and
+    # the file's last frame, 7 samples under the window's first weights, is one broad hump whose
+    # maximum any f32 spectrum places 0.3 Hz off, across a 10-cent boundary: the f32 CPU chain
+    # below misses the oracle's bins there exactly as the device does).  Measured on an MI355X:
+    # the oracle's bin set on 234 of 235 frames, salience deviation 1.900e-6 under 4 x 1.887e-6
+    frames = sorted(set(list(range(0, T, 3)) + [0, 1, T - 2, T - 1]))
+    set_ok = cnt_ok = 0
+    worst = yard = 0.0
     for t in frames:
         rb, rs = R.frame_salience_peaks(y, t)
         gb, gs = pk.frame(t)
         cnt_ok += abs(len(rb) - len(gb)) <= 1
-        if len(rb) == 0:
-            top_ok += len(gb) == 0
-            continue
-        top_ok += len(gb) > 0 and int(gb[0]) == int(rb[0])
-        ref = dict(zip(rb.astype(int).tolist(), rs.tolist()))
-        for b, s in zip(gb.astype(int).tolist(), gs.tolist()):
-            if b in ref:
-                worst = max(worst, abs(s - ref[b]) / max(1e-12, rs[0]))
-    assert top_ok >= 0.99 * len(frames), (top_ok, len(frames))
+        same, d = MC.salience_deviation((gb, gs), (rb, rs))     # the whole bin set, not the top bin only
+        set_ok += same
+        if same:
+            worst = max(worst, d)
+        # the yardstick: the oracle's stages on an f32 CPU spectrum of the same frame
+        same32, d32 = MC.salience_deviation(MC.as_output(MC.chain(MC.frame_mag32(y, t, R.HOP), 22050.0)), (rb, rs))
+        if same32:
+            yard = max(yard, d32)
+    print(f"bin sets {set_ok} of {len(frames)}, salience deviation {worst:.3e}, f32 CPU chain {yard:.3e}")
+    assert set_ok >= 0.99 * len(frames), (set_ok, len(frames))
     assert cnt_ok >= 0.99 * len(frames), (cnt_ok, len(frames))
-    assert worst < 1e-4, worst
+    assert worst <= 4.0 * yard, (worst, yard)
 
 
 def test_device_melody_equals_the_oracle_melody(eng):
