@@ -18,12 +18,14 @@
 
 #include "nc_block.h"
 #include "nc_decim.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
+#include "nc_ws.h"
 
 namespace nc {
 
 constexpr int AL_HOP = 512, AL_FRAME = 2048;
 
+// taken by value by the kernels; carved on the host by align_ws()
 struct AlignWs {
   int64_t* dec_base;  // [n_files + 1] decimated-signal offsets (64-float aligned)
   int64_t* env_base;  // [n_files + 1] envelope offsets
@@ -203,24 +205,32 @@ __global__ __launch_bounds__(256) void align_select_kernel(int n_speeds, int st_
   }
 }
 
-static inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // strides: st_stride >= envelope frames of the longest nc file, lag_stride >= max_off_frames + 1
 static void align_strides(int64_t max_len, int max_off_frames, int& st_stride, int& lag_stride) {
   st_stride = (int)(1 + ((max_len + 1) / 2) / AL_HOP);
   lag_stride = max_off_frames + 1;
 }
 
+// the one description of the workspace: sections in this order, each 256-byte aligned
+static AlignWs align_ws(WsCarve& c, int n_pairs, int n_speeds, int64_t total_len, int st_stride, int lag_stride) {
+  const int nf = 2 * n_pairs;
+  const size_t q = (size_t)n_pairs * n_speeds;
+  return {c.take<int64_t>(nf + 1),  // in AlignWs's member order (a braced list is evaluated left to right)
+          c.take<int64_t>(nf + 1),
+          c.take<int>(q),
+          c.take<int>(q),
+          c.take<float>((size_t)(total_len / 2 + 64 * (int64_t)nf + nf)),
+          c.take<double>((size_t)(total_len / 2 / AL_HOP + 2 * (int64_t)nf)),
+          c.take<double>(q * st_stride),
+          c.take<double>(q * lag_stride)};
+}
+
 size_t align_ws_bytes(int n_pairs, int n_speeds, int64_t total_len, int64_t max_len, int max_off_frames) {
   int st_stride, lag_stride;
   align_strides(max_len, max_off_frames, st_stride, lag_stride);
-  const int nf = 2 * n_pairs;
-  const size_t q = (size_t)n_pairs * n_speeds;
-  size_t b = al256(sizeof(int64_t) * (nf + 1)) * 2 + al256(sizeof(int) * q) * 2;
-  b += al256(sizeof(float) * (size_t)(total_len / 2 + 64 * (int64_t)nf + nf));
-  b += al256(sizeof(double) * (size_t)(total_len / 2 / AL_HOP + 2 * (int64_t)nf));
-  b += al256(sizeof(double) * q * st_stride) + al256(sizeof(double) * q * lag_stride);
-  return b + 4096;
+  WsCarve c;
+  align_ws(c, n_pairs, n_speeds, total_len, st_stride, lag_stride);
+  return c.bytes_plus(4096);
 }
 
 int launch_align_offsets(Context& ctx, const float* sig, const int64_t* src_off, const int64_t* src_len,
@@ -232,29 +242,15 @@ int launch_align_offsets(Context& ctx, const float* sig, const int64_t* src_off,
     set_error("align: n_speeds, max_offset_frames and max_len must be positive");
     return -2;
   }
-  if (ws_bytes < align_ws_bytes(n_pairs, n_speeds, total_len, max_len, max_off_frames)) {
+  int st_stride, lag_stride;
+  align_strides(max_len, max_off_frames, st_stride, lag_stride);
+  WsCarve c(ws);
+  const AlignWs w = align_ws(c, n_pairs, n_speeds, total_len, st_stride, lag_stride);
+  if (ws_bytes < c.bytes_plus(4096)) {
     set_error("align: workspace too small");
     return -3;
   }
-  int st_stride, lag_stride;
-  align_strides(max_len, max_off_frames, st_stride, lag_stride);
   const int nf = 2 * n_pairs;
-  const size_t q = (size_t)n_pairs * n_speeds;
-  char* c = static_cast<char*>(ws);
-  auto take = [&](size_t bytes) {
-    char* r = c;
-    c += al256(bytes);
-    return r;
-  };
-  AlignWs w;
-  w.dec_base = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * (nf + 1)));
-  w.env_base = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * (nf + 1)));
-  w.n_st = reinterpret_cast<int*>(take(sizeof(int) * q));
-  w.n_lag = reinterpret_cast<int*>(take(sizeof(int) * q));
-  w.dec = reinterpret_cast<float*>(take(sizeof(float) * (size_t)(total_len / 2 + 64 * (int64_t)nf + nf)));
-  w.env = reinterpret_cast<double*>(take(sizeof(double) * (size_t)(total_len / 2 / AL_HOP + 2 * (int64_t)nf)));
-  w.st = reinterpret_cast<double*>(take(sizeof(double) * q * st_stride));
-  w.corr = reinterpret_cast<double*>(take(sizeof(double) * q * lag_stride));
   hipLaunchKernelGGL(align_plan_kernel, dim3(1), dim3(256), 0, st, src_len, nc_len, n_pairs, speeds, n_speeds,
                      max_off_frames, w);
   const int64_t max_dec = (max_len + 1) / 2;

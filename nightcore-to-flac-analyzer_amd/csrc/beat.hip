@@ -18,7 +18,8 @@
 // Decision arithmetic is float64 throughout (as librosa's numba kernels), with
 // FMA contraction disabled where librosa adds separately rounded products.
 #include "nc_block.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
+#include "nc_ws.h"
 
 namespace nc {
 
@@ -713,9 +714,23 @@ int launch_ibi_from_beats(const int* beats, const int64_t* off, const int* nbeat
   return 0;
 }
 
-}  // namespace nc
+// the per-frame arrays of the workspace path, packed back to back
+struct BeatWs {
+  double *ls, *cum;
+  int* back;
+  uint8_t* marks;
+};
+static BeatWs beat_ws(WsCarve& c, int64_t total_frames) {
+  const size_t t = (size_t)total_frames;  // member order, evaluated left to right
+  return {c.take<double>(t, 8), c.take<double>(t, 8), c.take<int>(t, 4), c.take<uint8_t>(t, 1)};
+}
 
-namespace nc {
+size_t tempo_beats_ws_bytes(int64_t total_frames) {
+  WsCarve c;
+  beat_ws(c, total_frames);
+  return c.bytes_plus(256);
+}
+
 int launch_tempo_beats_c(Context& ctx, const float* onset, const int64_t* off, const int* len, int n_seq,
                          int max_len, const double* tg, int acw, const double* start_bpm, const int* prior_idx,
                          const uint8_t* active, int hop, int trim, double* bpm_out, int* lag_out,
@@ -738,11 +753,14 @@ int launch_tempo_beats_c(Context& ctx, const float* onset, const int64_t* off, c
   a.nbeats_out = nbeats_out;
   a.margin_out = margin_out;
   a.beats_out = beats_out;
-  if (ws && total_frames > 0 && ws_bytes >= (size_t)total_frames * 21) {
-    a.ws_ls = static_cast<double*>(ws);
-    a.ws_cum = a.ws_ls + total_frames;
-    a.ws_back = reinterpret_cast<int*>(a.ws_cum + total_frames);
-    a.ws_marks = reinterpret_cast<uint8_t*>(a.ws_back + total_frames);
+  WsCarve c(ws);
+  const BeatWs w = beat_ws(c, total_frames);
+  // a workspace that is missing or too small is no error: the kernels then keep these in LDS
+  if (ws && total_frames > 0 && ws_bytes >= c.bytes()) {
+    a.ws_ls = w.ls;
+    a.ws_cum = w.cum;
+    a.ws_back = w.back;
+    a.ws_marks = w.marks;
   }
   (void)ctx;
   return launch_tempo_beats(ctx, a, n_seq, max_len, st);

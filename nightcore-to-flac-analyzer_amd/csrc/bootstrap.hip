@@ -26,7 +26,8 @@
 // numpy's 'linear' method (virtual index (n-1) q, lerp with the t >= 0.5 branch),
 // whose (index, gamma) the host computes with numpy's own formula.
 #include "nc_block.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
+#include "nc_ws.h"
 
 namespace nc {
 
@@ -132,6 +133,7 @@ struct JobWs {
   uint16_t* cnt;
 };
 
+// (the host sizes this layout in bootstrap_job_bytes())
 __device__ __forceinline__ JobWs job_ws(const BootArgs& a, int j, int na) {
   const int cap = a.cap[j];
   char* w = a.ws + a.ws_off[j];
@@ -595,11 +597,17 @@ __global__ __launch_bounds__(BT) void bootstrap_finish_kernel(BootArgs a) {
   }
 }
 
+// one job's region, as job_ws() reads it on the device, closed to 256 bytes
 size_t bootstrap_job_bytes(int cap, int n_boot) {
-  size_t b = (((size_t)cap * 4 + 15) & ~(size_t)15);
-  b += (size_t)cap * 8 + (size_t)n_boot * 8 + (size_t)n_boot * 8 + sizeof(JobCtl) + 2 * REJ_CAP * 8 +
-       (size_t)n_boot * cap * 2;
-  return (b + 255) & ~(size_t)255;
+  WsCarve c;
+  c.skip((size_t)cap * sizeof(int), 16);                        // rank
+  c.skip((size_t)cap * sizeof(double), 8);                      // sorted
+  c.skip((size_t)n_boot * sizeof(int64_t), 8);                  // start
+  c.skip((size_t)n_boot * sizeof(double), 8);                   // boot
+  c.skip(sizeof(JobCtl) + 2 * REJ_CAP * sizeof(int64_t), 8);    // JobCtl, rejA, rejB
+  c.skip((size_t)n_boot * cap * sizeof(uint16_t), 2);           // counts
+  c.skip(0);
+  return c.bytes();
 }
 
 #ifndef NC_PROBE_SKIP_BOOT

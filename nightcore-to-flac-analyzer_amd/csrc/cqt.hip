@@ -18,11 +18,13 @@
 //   5. chroma_finalize_kernel mean over frames -> f32[12] per chunk
 //   6. chroma_lag_kernel      argmax_k dot(src, roll(nc, -k)), wrapped to [-5, 6]
 #include <algorithm>
+#include <type_traits>
 
 #include "nc_block.h"
 #include "nc_decim.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
 #include "nc_piptrack.h"
+#include "nc_ws.h"
 
 namespace nc {
 
@@ -1471,8 +1473,6 @@ struct ChromaWs {
   int64_t* cq_off;  // [n] after head: where the low-octave CQT reads each chunk (chroma_plan_kernel)
 };
 
-static inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // The one carving of the workspace: sections in this order, each 256-byte aligned.  The launcher
 // takes its pointers from it, chroma_ws_bytes its size, and nc_chroma_workspace_layout
 // (include/ncgpu.h, which documents every section) reports the same offsets.
@@ -1481,42 +1481,50 @@ enum ChromaSec {
   CS_WS_OCT, CS_PEAK_PITCH, CS_PEAK_MAG, CS_PARTIAL, CS_TP_BASE, CS_XMAX, CS_GPART, CS_OCT_EX, CS_HEAD, CS_COUNT
 };
 struct ChromaLayout {
+  ChromaWs w;
+  int64_t* tp_base;
   size_t off[CS_COUNT];
   size_t end;
 };
-static ChromaLayout chroma_layout(int n, int64_t total_len) {
+static ChromaLayout chroma_layout(WsCarve& c, int n, int64_t total_len) {
   // octave buffers: < total_len * (1/2 + ... ) + padding; tuning frames <= total_len/512 + n
-  const int64_t tfr = total_len / 512 + n;
+  const size_t tfr = (size_t)(total_len / 512 + n), nn = (size_t)n;
   const size_t oct_floats = (size_t)(total_len + 64 * 7 * (int64_t)n);
-  size_t bytes[CS_COUNT];
-  bytes[CS_OCT_OFF] = sizeof(int64_t) * 7 * n;
-  bytes[CS_OCT_LEN] = sizeof(int64_t) * 7 * n;
-  bytes[CS_N_FRAMES] = sizeof(int) * n;
-  bytes[CS_N_TFRAMES] = sizeof(int) * n;
-  bytes[CS_CHUNK_NPK] = sizeof(int) * n;
-  bytes[CS_TUNING_IDX] = sizeof(int) * n;
-  bytes[CS_TF_BASE] = sizeof(int64_t) * (n + 1);
-  bytes[CS_OCT_BASE] = sizeof(int64_t) * (n + 1);
-  bytes[CS_WS_OCT] = sizeof(float) * oct_floats;
-  bytes[CS_PEAK_PITCH] = sizeof(float) * (size_t)tfr * kPeakSlots;
-  bytes[CS_PEAK_MAG] = sizeof(float) * (size_t)tfr * kPeakSlots;
-  bytes[CS_PARTIAL] = sizeof(double) * (size_t)(tfr / CM_FR + n + 1) * 12;
-  bytes[CS_TP_BASE] = sizeof(int64_t) * (n + 1);
-  bytes[CS_XMAX] = sizeof(float) * (size_t)(n + oct_floats / 256 + 2);
-  bytes[CS_GPART] = sizeof(float) * (size_t)tfr * 84;
-  bytes[CS_OCT_EX] = sizeof(int) * 7 * n;
-  bytes[CS_HEAD] = (sizeof(float) * 4 + sizeof(int64_t)) * n;  // head [n][4], then cq_off [n]
   ChromaLayout l;
-  size_t p = 0;
-  for (int i = 0; i < CS_COUNT; ++i) {
-    l.off[i] = p;
-    p += al256(bytes[i]);
-  }
-  l.end = p;
+  ChromaWs& w = l.w;
+  auto sec = [&](ChromaSec s, auto*& p, size_t count) {  // the calls below are in ChromaSec order
+    l.off[s] = c.bytes();
+    p = c.take<std::remove_reference_t<decltype(*p)>>(count);
+  };
+  sec(CS_OCT_OFF, w.oct_off, 7 * nn);
+  sec(CS_OCT_LEN, w.oct_len, 7 * nn);
+  sec(CS_N_FRAMES, w.n_frames, nn);
+  sec(CS_N_TFRAMES, w.n_tframes, nn);
+  sec(CS_CHUNK_NPK, w.chunk_npk, nn);
+  sec(CS_TUNING_IDX, w.tuning_idx, nn);
+  sec(CS_TF_BASE, w.tf_base, nn + 1);
+  sec(CS_OCT_BASE, w.oct_base, nn + 1);
+  sec(CS_WS_OCT, w.ws_oct, oct_floats);
+  sec(CS_PEAK_PITCH, w.peak_pitch, tfr * kPeakSlots);
+  sec(CS_PEAK_MAG, w.peak_mag, tfr * kPeakSlots);
+  sec(CS_PARTIAL, w.partial, (tfr / CM_FR + nn + 1) * 12);
+  sec(CS_TP_BASE, l.tp_base, nn + 1);
+  sec(CS_XMAX, w.xmax, nn + oct_floats / 256 + 2);
+  sec(CS_GPART, w.gpart, tfr * 84);
+  sec(CS_OCT_EX, w.oct_ex, 7 * nn);
+  l.off[CS_HEAD] = c.bytes();  // head [n][4], then cq_off [n], closed to 256 bytes together
+  w.head = c.take<float>(4 * nn, 16);
+  w.cq_off = c.take<int64_t>(nn, 8);
+  c.skip(0);
+  l.end = c.bytes();
   return l;
 }
 
-size_t chroma_ws_bytes(int n, int64_t total_len) { return chroma_layout(n, total_len).end + 4096; }
+size_t chroma_ws_bytes(int n, int64_t total_len) {
+  WsCarve c;
+  chroma_layout(c, n, total_len);
+  return c.bytes_plus(4096);
+}
 
 // nc_chroma_workspace_layout: [0] entries written, [1 .. 16] section byte offsets in ChromaSec
 // order, the carved size, the tile constants the stage tests place edges by, then CS_HEAD's offset
@@ -1527,7 +1535,8 @@ int chroma_ws_layout_query(int n, int64_t total_len, int64_t* out, int cap) {
     set_error("chroma layout: needs n_chunks > 0, total_len >= 0 and room for 26 entries");  // kEntries
     return -2;
   }
-  const ChromaLayout l = chroma_layout(n, total_len);
+  WsCarve c;
+  const ChromaLayout l = chroma_layout(c, n, total_len);
   int k = 0;
   out[k++] = kEntries;
   for (int i = 0; i < CS_HEAD; ++i) out[k++] = (int64_t)l.off[i];
@@ -1554,7 +1563,9 @@ int launch_chroma_mean(Context& ctx, const float* sig, const int64_t* chunk_off,
     set_error("chroma: tf_skip needs the caller's peak lists (ext_pitch / ext_mag / ext_npk)");
     return -2;
   }
-  if (ws_bytes < chroma_ws_bytes(n, total_len)) {
+  WsCarve c(ws);
+  const ChromaLayout lay = chroma_layout(c, n, total_len);
+  if (ws_bytes < c.bytes_plus(4096)) {
     set_error("chroma: workspace too small");
     return -3;
   }
@@ -1562,29 +1573,11 @@ int launch_chroma_mean(Context& ctx, const float* sig, const int64_t* chunk_off,
     set_error("chroma: max_chunk_len must be positive");
     return -2;
   }
-  const ChromaLayout lay = chroma_layout(n, total_len);
-  auto sec = [&](ChromaSec s) { return static_cast<char*>(ws) + lay.off[s]; };
   const int64_t tfr = total_len / 512 + n;
-  ChromaWs w;
-  w.oct_off = reinterpret_cast<int64_t*>(sec(CS_OCT_OFF));
-  w.oct_len = reinterpret_cast<int64_t*>(sec(CS_OCT_LEN));
-  w.n_frames = reinterpret_cast<int*>(sec(CS_N_FRAMES));
-  w.n_tframes = reinterpret_cast<int*>(sec(CS_N_TFRAMES));
-  w.chunk_npk = reinterpret_cast<int*>(sec(CS_CHUNK_NPK));
+  ChromaWs w = lay.w;
+  int64_t* tp_base = lay.tp_base;
   // (the workspace's slot stays reserved when the caller gives its own array)
-  w.tuning_idx = out_tuning_idx ? out_tuning_idx : reinterpret_cast<int*>(sec(CS_TUNING_IDX));
-  w.tf_base = reinterpret_cast<int64_t*>(sec(CS_TF_BASE));
-  w.oct_base = reinterpret_cast<int64_t*>(sec(CS_OCT_BASE));
-  w.ws_oct = reinterpret_cast<float*>(sec(CS_WS_OCT));
-  w.peak_pitch = reinterpret_cast<float*>(sec(CS_PEAK_PITCH));
-  w.peak_mag = reinterpret_cast<float*>(sec(CS_PEAK_MAG));
-  w.partial = reinterpret_cast<double*>(sec(CS_PARTIAL));
-  int64_t* tp_base = reinterpret_cast<int64_t*>(sec(CS_TP_BASE));
-  w.xmax = reinterpret_cast<float*>(sec(CS_XMAX));
-  w.gpart = reinterpret_cast<float*>(sec(CS_GPART));
-  w.oct_ex = reinterpret_cast<int*>(sec(CS_OCT_EX));
-  w.head = reinterpret_cast<float*>(sec(CS_HEAD));
-  w.cq_off = reinterpret_cast<int64_t*>(sec(CS_HEAD) + sizeof(float) * 4 * n);
+  if (out_tuning_idx) w.tuning_idx = out_tuning_idx;
   if (ext) {  // the caller's lists (zeroed counts): the window stage appends to them too
     w.peak_pitch = ext_pitch;
     w.peak_mag = ext_mag;

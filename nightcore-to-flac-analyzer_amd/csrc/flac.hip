@@ -31,7 +31,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "nc_engine.h"
+#include "nc_launch.h"
 #include "nc_flac_crc.h"
 
 namespace nc {

@@ -29,7 +29,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "nc_engine.h"
+#include "nc_launch.h"
 #define NC_COHERENT_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #endif
 #include "nc_flac_crc.h"

@@ -12,7 +12,7 @@
 //   xcorr_peak_kernel     pitch._cyclic_xcorr_peak (pitch.py:67-85) for vectors of any
 //                         length n (the 12-bin chroma_lag_kernel is the batch path)
 #include "nc_block.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
 
 namespace nc {
 

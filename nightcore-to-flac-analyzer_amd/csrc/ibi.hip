@@ -12,8 +12,9 @@
 #include <algorithm>
 
 #include "nc_block.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
 #include "nc_slide.h"
+#include "nc_ws.h"
 #include "stft_args.h"
 
 namespace nc {
@@ -202,41 +203,38 @@ __global__ __launch_bounds__(256) void ibi_onset_range_kernel(const float* sdb, 
 }
 
 // ------------------------------------------------------------------------------ host
-static inline size_t a256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-size_t ibi_range_ws_bytes(int n_files, int64_t total_rows) {
-  return 4 * a256(sizeof(int64_t) * (n_files + 1)) + a256(sizeof(float) * (size_t)total_rows) +
-         a256(sizeof(float) * (size_t)total_rows * 128) + 4096;
-}
-
+// the workspace shared by nc_ibi_mel_range and nc_ibi_onset_range
 struct IbiRangeWs {
   int64_t *row0, *row_base, *obase;
   float *fmax_, *sdb;
 };
-static IbiRangeWs ibi_range_ws(void* ws, int n_files, int64_t total_rows) {
-  char* p = static_cast<char*>(ws);
+static IbiRangeWs ibi_range_ws(WsCarve& c, int n_files, int64_t total_rows) {
   IbiRangeWs w;
-  w.row0 = reinterpret_cast<int64_t*>(p);
-  p += a256(sizeof(int64_t) * (n_files + 1));
-  w.row_base = reinterpret_cast<int64_t*>(p);
-  p += a256(sizeof(int64_t) * (n_files + 1));
-  w.obase = reinterpret_cast<int64_t*>(p);
-  p += 2 * a256(sizeof(int64_t) * (n_files + 1));
-  w.fmax_ = reinterpret_cast<float*>(p);
-  p += a256(sizeof(float) * (size_t)total_rows);
-  w.sdb = reinterpret_cast<float*>(p);
+  w.row0 = c.take<int64_t>(n_files + 1);
+  w.row_base = c.take<int64_t>(n_files + 1);
+  w.obase = c.take<int64_t>(n_files + 1);
+  c.skip(sizeof(int64_t) * (n_files + 1));  // a fourth table, no longer used: the offsets below stay
+  w.fmax_ = c.take<float>((size_t)total_rows);
+  w.sdb = c.take<float>((size_t)total_rows * 128);
   return w;
+}
+
+size_t ibi_range_ws_bytes(int n_files, int64_t total_rows) {
+  WsCarve c;
+  ibi_range_ws(c, n_files, total_rows);
+  return c.bytes_plus(4096);
 }
 
 int launch_ibi_mel_range(Context& ctx, const float* sig, const int64_t* file_off, const int64_t* file_len,
                          int n_files, const int64_t* t0, const int64_t* t1, int hop, int64_t total_rows,
                          float* max_out, void* ws, size_t ws_bytes, hipStream_t st) {
   if (n_files <= 0) return 0;
-  if (ws_bytes < ibi_range_ws_bytes(n_files, total_rows)) {
+  WsCarve c(ws);
+  const IbiRangeWs w = ibi_range_ws(c, n_files, total_rows);
+  if (ws_bytes < c.bytes_plus(4096)) {
     set_error("ibi_mel_range: workspace too small");
     return -3;
   }
-  IbiRangeWs w = ibi_range_ws(ws, n_files, total_rows);
   const int pad = 1 + kNFFT / (2 * hop);
   hipLaunchKernelGGL(ibi_range_plan_kernel, dim3(1), dim3(256), 0, st, file_len, t0, t1, n_files, hop, pad, w.row0,
                      w.row_base, w.obase);
@@ -264,34 +262,42 @@ int launch_ibi_mel_range(Context& ctx, const float* sig, const int64_t* file_off
 int launch_ibi_onset_range(int n_files, const int64_t* t0, int hop, int64_t total_out, const float* gmax,
                            float* onset_out, void* ws, int64_t total_rows, hipStream_t st) {
   if (n_files <= 0 || total_out <= 0) return 0;
-  IbiRangeWs w = ibi_range_ws(ws, n_files, total_rows);
+  WsCarve c(ws);  // the workspace nc_ibi_mel_range checked and filled
+  const IbiRangeWs w = ibi_range_ws(c, n_files, total_rows);
   hipLaunchKernelGGL(ibi_onset_range_kernel, dim3((unsigned)((total_out + 3) / 4)), dim3(256), 0, st, w.sdb,
                      w.row_base, w.row0, t0, w.obase, gmax, n_files, total_out, 1 + kNFFT / (2 * hop), onset_out);
   NC_HIP(hipGetLastError());
   return 0;
 }
 
+struct IbiOnsetWs {
+  int64_t* fb;   // [n_files + 1] frame bases (the slot stays reserved under a caller's frame_base_out)
+  float* smax;   // [n_files] dB maxima
+  float* fmax_;  // [frame] row maxima
+  float* sdb;    // [frame][128] mel dB rows
+};
+static IbiOnsetWs ibi_onset_ws(WsCarve& c, int n_files, int64_t total_frames) {
+  return {c.take<int64_t>(n_files + 1), c.take<float>(n_files), c.take<float>((size_t)total_frames),
+          c.take<float>((size_t)total_frames * 128)};  // member order, evaluated left to right
+}
+
 size_t ibi_onset_ws_bytes(int n_files, int64_t total_frames) {
-  return a256(sizeof(int64_t) * (n_files + 1)) + a256(sizeof(float) * n_files) +
-         a256(sizeof(float) * (size_t)total_frames) + a256(sizeof(float) * (size_t)total_frames * 128) + 4096;
+  WsCarve c;
+  ibi_onset_ws(c, n_files, total_frames);
+  return c.bytes_plus(4096);
 }
 
 int launch_ibi_onset(Context& ctx, const float* sig, const int64_t* file_off, const int64_t* file_len, int n_files,
                      int64_t total_frames, int hop, float* onset_out, int64_t* frame_base_out, void* ws,
                      size_t ws_bytes, hipStream_t st) {
   if (n_files <= 0) return 0;
-  if (ws_bytes < ibi_onset_ws_bytes(n_files, total_frames)) {
+  WsCarve c(ws);
+  const IbiOnsetWs w = ibi_onset_ws(c, n_files, total_frames);
+  if (ws_bytes < c.bytes_plus(4096)) {
     set_error("ibi_onset: workspace too small");
     return -3;
   }
-  char* p = static_cast<char*>(ws);
-  int64_t* fb = frame_base_out ? frame_base_out : reinterpret_cast<int64_t*>(p);
-  p += a256(sizeof(int64_t) * (n_files + 1));
-  float* smax = reinterpret_cast<float*>(p);
-  p += a256(sizeof(float) * n_files);
-  float* fmax_ = reinterpret_cast<float*>(p);
-  p += a256(sizeof(float) * (size_t)total_frames);
-  float* sdb = reinterpret_cast<float*>(p);
+  int64_t* fb = frame_base_out ? frame_base_out : w.fb;
   hipLaunchKernelGGL(ibi_plan_kernel, dim3(1), dim3(256), 0, st, file_len, n_files, hop, fb);
   StftMelArgs s{};
   s.sig = sig;
@@ -301,14 +307,14 @@ int launch_ibi_onset(Context& ctx, const float* sig, const int64_t* file_off, co
   s.n_seq = n_files;
   s.total_frames = total_frames;
   s.hop = hop;
-  s.sdb = sdb;
-  s.frame_max = fmax_;
+  s.sdb = w.sdb;
+  s.frame_max = w.fmax_;
   s.frame_energy = nullptr;
   int rc = launch_stft_mel(ctx, s, st);
   if (rc) return rc;
-  hipLaunchKernelGGL(seq_max_kernel, dim3(n_files), dim3(256), 0, st, fmax_, fb, smax);
+  hipLaunchKernelGGL(seq_max_kernel, dim3(n_files), dim3(256), 0, st, w.fmax_, fb, w.smax);
   const unsigned blocks = (unsigned)((total_frames + 3) / 4);
-  hipLaunchKernelGGL(ibi_onset_kernel, dim3(blocks), dim3(256), 0, st, sdb, fb, smax, n_files, total_frames,
+  hipLaunchKernelGGL(ibi_onset_kernel, dim3(blocks), dim3(256), 0, st, w.sdb, fb, w.smax, n_files, total_frames,
                      1 + kNFFT / (2 * hop), onset_out);
   NC_HIP(hipGetLastError());
   return 0;
@@ -316,16 +322,22 @@ int launch_ibi_onset(Context& ctx, const float* sig, const int64_t* file_off, co
 
 static int tg_acw(const Context& ctx, int hop) { return hop == 64 ? ctx.t.ac64 : (hop == 512 ? ctx.t.ac512 : 0); }
 
-size_t ibi_tg_ws_bytes(const Context& ctx, int n_files, int64_t total_frames, int max_frames, int hop) {
-  const int N = tg_acw(ctx, hop);
-  const int n_tblk = (max_frames + TG_TB - 1) / TG_TB;
-  return a256(sizeof(float) * ((size_t)total_frames + (size_t)n_files * N)) +
-         a256(sizeof(double) * (size_t)total_frames) + a256(sizeof(double) * (size_t)n_files * n_tblk * N) + 256;
+struct IbiTgWs {
+  float* xpad;   // [total_frames + n_files * N] ramp-padded onsets
+  double* rinv;  // [frame] normalisers
+  double* slab;  // [file][n_tblk][N] tile rows (the slot stays reserved under a caller's slab_out)
+};
+// N = tg_acw(ctx, hop), n_tblk = tiles of the longest file
+static IbiTgWs ibi_tg_ws(WsCarve& c, int n_files, int64_t total_frames, int n_tblk, int N) {
+  return {c.take<float>((size_t)total_frames + (size_t)n_files * N), c.take<double>((size_t)total_frames),
+          c.take<double>((size_t)n_files * n_tblk * N)};  // member order, evaluated left to right
 }
 
-int launch_ibi_tempogram_tiles(Context& ctx, const float* onset, const int64_t* frame_base, int n_files,
-                               int64_t total_frames, int max_frames, int hop, const int64_t* b0, const int64_t* b1,
-                               double* slab_out, double* tg_out, void* ws, size_t ws_bytes, hipStream_t st);
+size_t ibi_tg_ws_bytes(const Context& ctx, int n_files, int64_t total_frames, int max_frames, int hop) {
+  WsCarve c;
+  ibi_tg_ws(c, n_files, total_frames, (max_frames + TG_TB - 1) / TG_TB, tg_acw(ctx, hop));
+  return c.bytes_plus(256);
+}
 
 int launch_ibi_tempogram(Context& ctx, const float* onset, const int64_t* frame_base, int n_files,
                          int64_t total_frames, int max_frames, int hop, double* tg_out, void* ws, size_t ws_bytes,
@@ -363,25 +375,22 @@ int launch_ibi_tempogram_tiles(Context& ctx, const float* onset, const int64_t* 
     set_error("ibi_tempogram: max_frames out of range");
     return -2;
   }
-  if (ws_bytes < ibi_tg_ws_bytes(ctx, n_files, total_frames, max_frames, hop)) {
+  const int n_tblk = (max_frames + TG_TB - 1) / TG_TB;
+  WsCarve c(ws);
+  const IbiTgWs w = ibi_tg_ws(c, n_files, total_frames, n_tblk, N);
+  if (ws_bytes < c.bytes_plus(256)) {
     set_error("ibi_tempogram: workspace too small");
     return -3;
   }
-  const int n_tblk = (max_frames + TG_TB - 1) / TG_TB;
   const int64_t total_padded = total_frames + (int64_t)n_files * N;
-  char* p = static_cast<char*>(ws);
-  float* xpad = reinterpret_cast<float*>(p);
-  p += a256(sizeof(float) * (size_t)total_padded);
-  double* rinv = reinterpret_cast<double*>(p);
-  p += a256(sizeof(double) * (size_t)total_frames);
-  double* slab = slab_out ? slab_out : reinterpret_cast<double*>(p);
+  double* slab = slab_out ? slab_out : w.slab;
   hipLaunchKernelGGL(tg_pad_kernel, dim3((unsigned)((total_padded + 255) / 256)), dim3(256), 0, st, onset,
-                     frame_base, n_files, total_padded, N, xpad);
-  hipLaunchKernelGGL(tg_rinv_kernel, dim3((unsigned)((total_frames + 255) / 256)), dim3(256), 0, st, xpad,
-                     frame_base, n_files, total_frames, N, hop == 64 ? ctx.t.wsq64 : ctx.t.wsq512, b0, b1, rinv);
+                     frame_base, n_files, total_padded, N, w.xpad);
+  hipLaunchKernelGGL(tg_rinv_kernel, dim3((unsigned)((total_frames + 255) / 256)), dim3(256), 0, st, w.xpad,
+                     frame_base, n_files, total_frames, N, hop == 64 ? ctx.t.wsq64 : ctx.t.wsq512, b0, b1, w.rinv);
   TgSlideArgs a;
-  a.xpad = xpad;
-  a.rinv = rinv;
+  a.xpad = w.xpad;
+  a.rinv = w.rinv;
   a.frame_base = frame_base;
   a.N = N;
   a.n_tblk = n_tblk;

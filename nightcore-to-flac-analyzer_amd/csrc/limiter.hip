@@ -37,7 +37,8 @@
 #include <cmath>
 
 #include "nc_device.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
+#include "nc_ws.h"
 
 namespace nc {
 
@@ -73,9 +74,7 @@ struct LimPow {
 // carry[tiles] f64, a multiple of 256 bytes
 __host__ __device__ inline int64_t lim_pad(int64_t n) { return (n + 63) / 64 * 64; }
 __host__ __device__ inline int64_t lim_tiles(int64_t n) { return (n + LM_T - 1) / LM_T; }
-__host__ __device__ inline int64_t lim_file_bytes(int64_t n) {
-  return (lim_pad(n) * 8 + lim_tiles(n) * 16 + 255) / 256 * 256;
-}
+// (LimWs reads on the device what lim_file_carve() lays out on the host)
 struct LimWs {
   float* r;
   float* dl;
@@ -455,19 +454,30 @@ __global__ __launch_bounds__(LM_AP_THREADS) void limiter_apply_kernel(
   }
 }
 
+// the region of a file of n frames, appended to the files before it; returns its offset
+static size_t lim_file_carve(WsCarve& c, int64_t n) {
+  const size_t off = c.bytes(), pad = (size_t)lim_pad(n), tiles = (size_t)lim_tiles(n);
+  c.skip(pad * sizeof(float), 4);     // r
+  c.skip(pad * sizeof(float), 4);     // local d
+  c.skip(tiles * sizeof(double), 8);  // agg
+  c.skip(tiles * sizeof(double), 8);  // carry
+  c.skip(0);
+  return off;
+}
+
 // nc_limiter_ws_bytes: the files' regions back to back
 size_t limiter_ws_bytes(const int64_t* n_frames, int n_files, int64_t* ws_off) {
-  int64_t tot = 0;
+  WsCarve c;
   for (int f = 0; f < n_files; ++f) {
-    if (ws_off) ws_off[f] = tot;
-    tot += lim_file_bytes(std::max<int64_t>(0, n_frames[f]));
+    const size_t off = lim_file_carve(c, std::max<int64_t>(0, n_frames[f]));
+    if (ws_off) ws_off[f] = (int64_t)off;
   }
-  return (size_t)tot;
+  return c.bytes();
 }
 
 // the groups of one call, from the host's copy of the descriptors
 static int lim_check(const char* who, const int64_t* host_len, const int* host_first, int n_files, int64_t* max_len,
-                     int64_t* ws_need) {
+                     size_t* ws_need) {
   const std::string w(who);
   if (n_files > 65535) {
     set_error(w + ": at most 65535 files in one call");
@@ -477,7 +487,8 @@ static int lim_check(const char* who, const int64_t* host_len, const int* host_f
     set_error(w + ": host_len and host_first (starting at 0) are required");
     return -2;
   }
-  *max_len = 0, *ws_need = 0;
+  *max_len = 0;
+  WsCarve c;
   for (int f = 0; f < n_files; ++f) {
     const int s0 = host_first[f], C = host_first[f + 1] - s0;
     if (C < 1) {
@@ -495,8 +506,9 @@ static int lim_check(const char* who, const int64_t* host_len, const int* host_f
         return -2;
       }
     *max_len = std::max(*max_len, n);
-    *ws_need += lim_file_bytes(n);
+    lim_file_carve(c, n);
   }
+  *ws_need = c.bytes();
   return 0;
 }
 
@@ -504,7 +516,8 @@ int launch_true_peak(Context& ctx, const float* x, const int64_t* sig_off, const
                      const int* file_first, const int64_t* host_len, const int* host_first, int n_files,
                      float* true_peak, hipStream_t st) {
   if (n_files <= 0) return 0;
-  int64_t max_len, need;
+  int64_t max_len;
+  size_t need;
   if (int rc = lim_check("true_peak", host_len, host_first, n_files, &max_len, &need)) return rc;
   NC_HIP(hipMemsetAsync(true_peak, 0, (size_t)n_files * sizeof(float), st));
   if (max_len <= 0) return 0;
@@ -533,9 +546,10 @@ int launch_true_peak_limit(Context& ctx, const float* x, const int64_t* sig_off,
     set_error("true_peak_limit: attack outside 1 .. 2048 samples, or release below 1 sample");
     return -2;
   }
-  int64_t max_len, need;
+  int64_t max_len;
+  size_t need;
   if (int rc = lim_check("true_peak_limit", host_len, host_first, n_files, &max_len, &need)) return rc;
-  if ((size_t)need > ws_bytes || (need > 0 && (!ws || !ws_off))) {
+  if (need > ws_bytes || (need > 0 && (!ws || !ws_off))) {
     set_error("true_peak_limit: workspace smaller than nc_limiter_ws_bytes");
     return -2;
   }

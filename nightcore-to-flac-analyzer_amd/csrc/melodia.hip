@@ -42,7 +42,7 @@
 #include <algorithm>
 
 #include "nc_block.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
 
 namespace nc {
 

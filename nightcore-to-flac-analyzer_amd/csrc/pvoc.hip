@@ -36,7 +36,8 @@
 #include <algorithm>
 
 #include "nc_device.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
+#include "nc_ws.h"
 
 namespace nc {
 
@@ -68,10 +69,30 @@ __host__ __device__ inline int64_t pv_scan_rows(int64_t total_frames, int n_file
 // (floor(a + b) >= floor(a) + floor(b), and the + f leaves room for every file's partial tile)
 __device__ __forceinline__ int64_t pv_row0(int64_t fb, int f) { return fb / PV_TILE + f; }
 
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t pv_scan_ws_bytes(int64_t total_frames, int n_files) {
+struct PvScanWs {
+  double2 *agg, *carry;  // [row][bin] tile aggregates, Phi of the frame before each tile
+  uint8_t* aflag;        // [row]
+};
+static PvScanWs pv_scan_ws(WsCarve& c, int64_t total_frames, int n_files) {
   const size_t rows = (size_t)pv_scan_rows(total_frames, n_files);
-  return al256(rows * PV_BINS * sizeof(double2)) * 2 + al256(rows);
+  return {c.take<double2>(rows * PV_BINS), c.take<double2>(rows * PV_BINS), c.take<uint8_t>(rows)};  // member order
+}
+size_t pv_scan_ws_bytes(int64_t total_frames, int n_files) {
+  WsCarve c;
+  pv_scan_ws(c, total_frames, n_files);
+  return c.bytes();
+}
+
+// The six sections of nc_pv_stretch's workspace, in bytes: mag, V, Phi, frame buffer, empty, scan
+// workspace.  pv_plan lays them out 256-byte aligned; launch_pv_stretch holds the caller's
+// offsets against them.
+static void pv_stretch_sizes(int64_t total_frames, int n_files, size_t sizes[6]) {
+  const size_t t = (size_t)total_frames;
+  sizes[0] = t * PV_BINS * sizeof(float);
+  sizes[1] = sizes[2] = t * PV_BINS * sizeof(float2);
+  sizes[3] = t * PV_N * sizeof(float);
+  sizes[4] = t;
+  sizes[5] = pv_scan_ws_bytes(total_frames, n_files);
 }
 
 // Host plan: ns / k per file, frame_base [n_files + 1], and the workspace of nc_pv_stretch:
@@ -99,15 +120,14 @@ int pv_plan(int64_t P, const int64_t* n_in, int n_files, int64_t* ns_out, int64_
     total += k;
   }
   if (frame_base) frame_base[n_files] = total;
-  const size_t t = (size_t)total;
-  size_t off = 0;
-  const size_t sizes[6] = {t * PV_BINS * sizeof(float), t * PV_BINS * sizeof(float2), t * PV_BINS * sizeof(float2),
-                           t * PV_N * sizeof(float), t, pv_scan_ws_bytes(total, n_files)};
+  size_t sizes[6];
+  pv_stretch_sizes(total, n_files, sizes);
+  WsCarve c;
   for (int i = 0; i < 6; ++i) {
-    if (ws_off) ws_off[i] = (int64_t)off;
-    off += al256(sizes[i]);
+    if (ws_off) ws_off[i] = (int64_t)c.bytes();
+    c.skip(sizes[i]);
   }
-  if (ws_bytes) *ws_bytes = off;
+  if (ws_bytes) *ws_bytes = c.bytes();
   return 0;
 }
 
@@ -360,7 +380,9 @@ int launch_pv_scan(Context& ctx, const float2* V, const uint8_t* empty, const in
     set_error("pv_scan: null argument");
     return -2;
   }
-  if (ws_bytes < pv_scan_ws_bytes(total_frames, n_files)) {
+  WsCarve c(ws);
+  const PvScanWs w = pv_scan_ws(c, total_frames, n_files);
+  if (ws_bytes < c.bytes()) {
     set_error("pv_scan: workspace below nc_pv_plan's scan size");
     return -2;
   }
@@ -369,11 +391,7 @@ int launch_pv_scan(Context& ctx, const float2* V, const uint8_t* empty, const in
     set_error("pv_scan: max_frames must be the longest file's frame count (1 .. 65535 tiles), ws 16-byte aligned");
     return -2;
   }
-  const size_t rows = (size_t)pv_scan_rows(total_frames, n_files);
-  char* w = static_cast<char*>(ws);
-  PvScanArgs a{V, empty, frame_base, phi, reinterpret_cast<double2*>(w),
-               reinterpret_cast<double2*>(w + al256(rows * PV_BINS * sizeof(double2))),
-               reinterpret_cast<uint8_t*>(w + 2 * al256(rows * PV_BINS * sizeof(double2))), nullptr};
+  PvScanArgs a{V, empty, frame_base, phi, w.agg, w.carry, w.aflag, nullptr};
   const unsigned bx = (PV_BINS + 255) / 256;
   const dim3 gt(bx, (unsigned)max_tiles, (unsigned)n_files);
   {
@@ -594,22 +612,21 @@ struct PvLockArgs {
   unsigned long long* span;
 };
 
-static size_t pv_lock_ws_layout(int64_t total_frames, int n_files, size_t off[5]) {
+struct PvLockWs {
+  float2* M;             // [frame][bin]
+  uint16_t* owner;       // [frame][bin] (the slot stays reserved under a caller's owner array)
+  double2 *agg, *carry;  // [row][bin]
+  uint16_t* asrc;        // [row][bin]
+};
+static PvLockWs pv_lock_ws(WsCarve& c, int64_t total_frames, int n_files) {
   const size_t t = (size_t)total_frames, rows = (size_t)pv_scan_rows(total_frames, n_files);
-  const size_t sizes[5] = {t * PV_BINS * sizeof(float2), t * PV_BINS * sizeof(uint16_t),
-                           rows * PV_BINS * sizeof(double2), rows * PV_BINS * sizeof(double2),
-                           rows * PV_BINS * sizeof(uint16_t)};
-  size_t o = 0;
-  for (int i = 0; i < 5; ++i) {
-    off[i] = o;
-    o += al256(sizes[i]);
-  }
-  return o;
+  return {c.take<float2>(t * PV_BINS), c.take<uint16_t>(t * PV_BINS), c.take<double2>(rows * PV_BINS),
+          c.take<double2>(rows * PV_BINS), c.take<uint16_t>(rows * PV_BINS)};  // member order, left to right
 }
-// M, owner, agg, carry, asrc
 size_t pv_lock_ws_bytes(int64_t total_frames, int n_files) {
-  size_t off[5];
-  return pv_lock_ws_layout(total_frames, n_files, off);
+  WsCarve c;
+  pv_lock_ws(c, total_frames, n_files);
+  return c.bytes();
 }
 
 __device__ __forceinline__ double2 pv_mul64(double2 p, double2 v) {
@@ -839,8 +856,9 @@ int launch_pv_lock(Context& ctx, const float* mag, const float2* U, const float2
     set_error("pv_lock: null argument");
     return -2;
   }
-  size_t off[5];
-  if (ws_bytes < pv_lock_ws_layout(total_frames, n_files, off)) {
+  WsCarve c(ws);
+  const PvLockWs w = pv_lock_ws(c, total_frames, n_files);
+  if (ws_bytes < c.bytes()) {
     set_error("pv_lock: workspace below nc_pv_lock_ws_bytes");
     return -2;
   }
@@ -849,11 +867,8 @@ int launch_pv_lock(Context& ctx, const float* mag, const float2* U, const float2
     set_error("pv_lock: max_frames must be the longest file's frame count (at least 1), ws 16-byte aligned");
     return -2;
   }
-  char* w = static_cast<char*>(ws);
-  PvLockArgs a{mag, U, V, empty, frame_base, n_files, total_frames,
-               owner ? owner : reinterpret_cast<uint16_t*>(w + off[1]), reinterpret_cast<float2*>(w + off[0]), phi,
-               reinterpret_cast<double2*>(w + off[2]), reinterpret_cast<uint16_t*>(w + off[4]),
-               reinterpret_cast<double2*>(w + off[3]), nullptr};
+  PvLockArgs a{mag, U, V, empty, frame_base, n_files, total_frames, owner ? owner : w.owner, w.M, phi,
+               w.agg, w.asrc, w.carry, nullptr};
   const dim3 gt((unsigned)max_tiles, (unsigned)n_files);
   {
     KTimer kt_(ctx, "pv_lock_prep", st);
@@ -1005,6 +1020,47 @@ int launch_pv_rotate(Context& ctx, const float2* psi, const float2* u_mid, const
   }
   NC_HIP(hipGetLastError());
   return 0;
+}
+
+// nc_pv_stretch: analysis, scan and synthesis on one workspace laid out by the caller (ws_off,
+// as pv_plan returns it or roomier)
+int launch_pv_stretch(Context& ctx, const float* x, const int64_t* in_off, const int64_t* in_len,
+                      const int64_t* frame_base, int n_files, int64_t total_frames, int64_t max_frames, int64_t P,
+                      int64_t max_ns, float* s, const int64_t* out_off, float* peak, void* ws, const int64_t* ws_off,
+                      size_t ws_bytes, hipStream_t st) {
+  if (n_files < 0 || total_frames < 0) {
+    set_error("nc_pv_stretch: negative file or frame count");
+    return -2;
+  }
+  size_t need[6];
+  pv_stretch_sizes(total_frames, std::max(0, n_files), need);
+  if (total_frames > 0) {
+    if (!ws || !ws_off) {
+      set_error("nc_pv_stretch: null workspace");
+      return -2;
+    }
+    for (int i = 0; i < 6; ++i) {
+      const int64_t end = i + 1 < 6 ? ws_off[i + 1] : (int64_t)ws_bytes;
+      if (ws_off[i] < 0 || (ws_off[i] & 15) || end < ws_off[i] || (size_t)(end - ws_off[i]) < need[i] ||
+          (size_t)end > ws_bytes) {
+        set_error("nc_pv_stretch: workspace below nc_pv_plan's layout");
+        return -2;
+      }
+    }
+  }
+  auto sec = [&](int i) { return total_frames > 0 ? static_cast<char*>(ws) + ws_off[i] : nullptr; };
+  float* mag = reinterpret_cast<float*>(sec(0));
+  float2 *v = reinterpret_cast<float2*>(sec(1)), *phi = reinterpret_cast<float2*>(sec(2));
+  float* frames = reinterpret_cast<float*>(sec(3));
+  uint8_t* empty = reinterpret_cast<uint8_t*>(sec(4));
+  int rc = launch_pv_analyze(ctx, x, in_off, in_len, frame_base, n_files, total_frames, P, mag, v, empty, nullptr,
+                             false, st);
+  if (rc) return rc;
+  rc = launch_pv_scan(ctx, v, empty, frame_base, n_files, total_frames, max_frames, phi, sec(5),
+                      total_frames > 0 ? ws_bytes - (size_t)ws_off[5] : 0, st);
+  if (rc) return rc;
+  return launch_pv_synth(ctx, mag, phi, in_len, frame_base, n_files, total_frames, P, max_ns, frames, need[3], s,
+                         out_off, peak, st);
 }
 
 }  // namespace nc

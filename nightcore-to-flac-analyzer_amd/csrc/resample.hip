@@ -19,7 +19,7 @@
 // launch (grid.y = file).
 #include <algorithm>
 
-#include "nc_engine.h"
+#include "nc_launch.h"
 
 namespace nc {
 

@@ -24,7 +24,8 @@
 #include <algorithm>
 
 #include "nc_block.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
+#include "nc_ws.h"
 
 namespace nc {
 
@@ -380,12 +381,22 @@ __global__ void spectral_bins_finish(const int64_t* frame_base, const double* pa
 // frames per bins-kernel block: at least 32, at most 256 blocks per file
 static int spectral_fb(int64_t max_frames) { return (int)std::max<int64_t>(32, (max_frames + 255) / 256); }
 
-size_t spectral_ws_bytes(int64_t total_frames, int n_files, int64_t max_frames) {
+struct SpectralWs {
+  float* rows;      // [frame][SF_ROW] dB rows
+  double* rec;      // [frame][SF_REC] per-frame records
+  double* partial;  // [file][nblk][SF_BINS] bins-kernel block sums
+};
+static SpectralWs spectral_ws(WsCarve& c, int64_t total_frames, int n_files, int64_t max_frames) {
   const int fb = spectral_fb(max_frames);
   const int64_t nblk = (max_frames + fb - 1) / fb;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  return al((size_t)total_frames * SF_ROW * sizeof(float)) + al((size_t)total_frames * SF_REC * sizeof(double)) +
-         al((size_t)n_files * nblk * SF_BINS * sizeof(double));
+  return {c.take<float>((size_t)total_frames * SF_ROW), c.take<double>((size_t)total_frames * SF_REC),
+          c.take<double>((size_t)n_files * nblk * SF_BINS)};  // member order, evaluated left to right
+}
+
+size_t spectral_ws_bytes(int64_t total_frames, int n_files, int64_t max_frames) {
+  WsCarve c;
+  spectral_ws(c, total_frames, n_files, max_frames);
+  return c.bytes();
 }
 
 int launch_spectral(Context& ctx, const float* sig, const int64_t* file_off, const int64_t* file_len,
@@ -401,20 +412,15 @@ int launch_spectral(Context& ctx, const float* sig, const int64_t* file_off, con
     set_error("spectral: roll_percent must lie in (0, 1)");  // spectral_rolloff's own check
     return -2;
   }
-  if (ws_bytes < spectral_ws_bytes(total_frames, n_files, max_frames)) {
+  WsCarve c(ws);
+  const SpectralWs w = spectral_ws(c, total_frames, n_files, max_frames);
+  if (ws_bytes < c.bytes()) {
     set_error("spectral: workspace too small");
     return -2;
   }
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  char* w = static_cast<char*>(ws);
-  float* rows = reinterpret_cast<float*>(w);
-  w += al((size_t)total_frames * SF_ROW * sizeof(float));
-  double* rec = reinterpret_cast<double*>(w);
-  w += al((size_t)total_frames * SF_REC * sizeof(double));
-  double* partial = reinterpret_cast<double*>(w);
 
   SpecArgs a{sig, file_off, file_len, frame_base, bin_hz, band_bins, n_files, total_frames, roll_percent,
-             rms_out, rows, rec, ctx.t.tw, ctx.t.hann2048};
+             rms_out, w.rows, w.rec, ctx.t.tw, ctx.t.hann2048};
   const size_t lds = spectral_frames_lds_bytes();
   const int64_t n_groups = (total_frames + SF_WAVES - 1) / SF_WAVES;
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(n_groups, (int64_t)ctx.num_cu));
@@ -424,19 +430,19 @@ int launch_spectral(Context& ctx, const float* sig, const int64_t* file_off, con
     hipLaunchKernelGGL(spectral_frames_kernel, dim3(grid), dim3(SF_THREADS), lds, st, a);
   }
   NC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(spectral_file_kernel<1024>, dim3(n_files), dim3(1024), 0, st, frame_base, rec, rms_out,
+  hipLaunchKernelGGL(spectral_file_kernel<1024>, dim3(n_files), dim3(1024), 0, st, frame_base, w.rec, rms_out,
                      stats_out);
   NC_HIP(hipGetLastError());
   const int fb = spectral_fb(max_frames);
   const int nblk = (int)((max_frames + fb - 1) / fb);
   {
     KTimer kt_(ctx, "spectral_bins", st);
-    hipLaunchKernelGGL(spectral_bins_kernel, dim3(nblk, n_files), dim3(SB_NT), 0, st, frame_base, rows,
-                       stats_out, fb, nblk, partial, kt_.span());
+    hipLaunchKernelGGL(spectral_bins_kernel, dim3(nblk, n_files), dim3(SB_NT), 0, st, frame_base, w.rows,
+                       stats_out, fb, nblk, w.partial, kt_.span());
   }
   NC_HIP(hipGetLastError());
   hipLaunchKernelGGL(spectral_bins_finish, dim3((SF_BINS + 255) / 256, n_files), dim3(256), 0, st, frame_base,
-                     partial, fb, nblk, bin_db_out);
+                     w.partial, fb, nblk, bin_db_out);
   NC_HIP(hipGetLastError());
   return 0;
 }

@@ -23,7 +23,7 @@
 #include <cmath>
 
 #include "nc_device.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
 
 namespace nc {
 

@@ -17,7 +17,7 @@
 #include <algorithm>
 
 #include "nc_block.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
 #include "nc_piptrack.h"
 
 #include "stft_args.h"

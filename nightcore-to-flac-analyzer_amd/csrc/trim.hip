@@ -9,7 +9,8 @@
 // read once from HBM); kernel 2: one workgroup per file forms each frame's mean
 // from its 4 blocks, then the max and the first/last frames above -top_db.
 #include "nc_block.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
+#include "nc_ws.h"
 
 namespace nc {
 
@@ -132,10 +133,24 @@ __global__ __launch_bounds__(256) void trim_bounds_kernel(const double* blk_all,
   }
 }
 
+// the two tables and the block sums, packed at 8 bytes (window_energy_blocks_kernel reads the
+// same layout from the workspace pointer)
+struct TrimWs {
+  int64_t* frame_base;  // [n_files + 1]
+  int64_t* tile_base;   // [n_files + 1]
+  double* blk;          // [frames] 512-sample block sums of x^2
+};
+static TrimWs trim_carve(WsCarve& c, int n_files, int64_t frames) {
+  return {c.take<int64_t>((size_t)(n_files + 1), 8), c.take<int64_t>((size_t)(n_files + 1), 8),
+          c.take<double>((size_t)frames, 8)};  // member order, evaluated left to right
+}
+
 size_t trim_ws_bytes(const int64_t* host_file_len, int n_files) {
-  size_t frames = 0;
+  int64_t frames = 0;
   for (int f = 0; f < n_files; ++f) frames += 1 + host_file_len[f] / 512;
-  return frames * sizeof(double) + 2 * (size_t)(n_files + 1) * sizeof(int64_t) + 256;
+  WsCarve c;
+  trim_carve(c, n_files, frames);
+  return c.bytes_plus(256);
 }
 
 // frame_base is computed on the device from file_len (parallel exclusive scan, one block)
@@ -152,25 +167,23 @@ int launch_trim(Context& ctx, const float* sig, const int64_t* file_off, const i
   (void)ctx;
   if (n_files <= 0) return 0;
   // max_frames = total frames over all files (host knows the lengths)
-  const size_t need = (size_t)max_frames * sizeof(double) + 2 * (size_t)(n_files + 1) * sizeof(int64_t);
-  if (ws_bytes < need) {
+  WsCarve c(ws);
+  const TrimWs w = trim_carve(c, n_files, max_frames);
+  if (ws_bytes < c.bytes()) {  // the size query's 256 bytes of slack are not required
     set_error("trim: workspace too small");
     return -3;
   }
-  int64_t* frame_base = static_cast<int64_t*>(ws);
-  int64_t* tile_base = frame_base + n_files + 1;
-  double* blk = reinterpret_cast<double*>(tile_base + n_files + 1);
-  hipLaunchKernelGGL(frame_base_kernel, dim3(1), dim3(256), 0, st, file_len, n_files, frame_base, tile_base);
+  hipLaunchKernelGGL(frame_base_kernel, dim3(1), dim3(256), 0, st, file_len, n_files, w.frame_base, w.tile_base);
   // tiles <= sum over files of ceil(blocks / TR_BPG) <= max_frames / TR_BPG + n_files
   const int64_t tiles = max_frames / TR_BPG + n_files + 1;
   {
     KTimer kt_(ctx, "trim_blocks", st);
     hipLaunchKernelGGL(trim_blocks_kernel, dim3((unsigned)tiles), dim3(256), 0, st, sig, file_off, file_len,
-                       frame_base, tile_base, n_files, blk, kt_.span());
+                       w.frame_base, w.tile_base, n_files, w.blk, kt_.span());
   }
   {
     MarkSpan ms_(ctx, "trim_bounds", st);
-    hipLaunchKernelGGL(trim_bounds_kernel, dim3(n_files), dim3(256), 0, st, blk, frame_base, file_len, top_db,
+    hipLaunchKernelGGL(trim_bounds_kernel, dim3(n_files), dim3(256), 0, st, w.blk, w.frame_base, file_len, top_db,
                        out_start, out_end);
   }
   NC_HIP(hipGetLastError());
@@ -191,7 +204,7 @@ __global__ __launch_bounds__(256) void window_energy_blocks_kernel(const float* 
   const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= n_win) return;
   const int f = win_file[w];
-  const int64_t* frame_base = trim_ws;
+  const int64_t* frame_base = trim_ws;  // the layout of the host's trim_carve()
   const double* blk = reinterpret_cast<const double*>(trim_ws + 2 * (n_files + 1)) + frame_base[f];
   const int64_t fo = file_off[f];
   const int64_t s = win_off[w] - fo, e = s + L;

@@ -15,9 +15,10 @@
 #include <algorithm>
 
 #include "nc_block.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
 #include "nc_slide.h"
 #include "nc_tgcorr.h"
+#include "nc_ws.h"
 
 #include "stft_args.h"
 
@@ -342,11 +343,20 @@ __global__ __launch_bounds__(WS_THREADS) void window_tg_slide_kernel(WinTgArgs a
   for (int k = tid; k < acw; k += WS_THREADS) a.tg_out[(size_t)w * acw + k] = part[k] / (double)T;
 }
 
-static inline size_t a256(size_t n) { return (n + 255) & ~(size_t)255; }
+struct WindowWs {
+  float* sdb;    // [frame][128] mel dB rows
+  float* fmax_;  // [frame] row maxima
+  double* fen;   // [frame] frame energies
+};
+static WindowWs window_stage_ws(WsCarve& c, int n_win, int T) {
+  const size_t F = (size_t)n_win * T;
+  return {c.take<float>(F * 128), c.take<float>(F), c.take<double>(F)};  // member order, left to right
+}
 
 size_t window_stage_ws_bytes(const Context&, int n_win, int T) {
-  const size_t F = (size_t)n_win * T;
-  return a256(F * 128 * sizeof(float)) + a256(F * sizeof(float)) + a256(F * sizeof(double));
+  WsCarve c;
+  window_stage_ws(c, n_win, T);
+  return c.bytes();
 }
 
 int launch_window_stage(Context& ctx, const float* sig, const int64_t* win_off, const uint8_t* active,
@@ -361,17 +371,13 @@ int launch_window_stage(Context& ctx, const float* sig, const int64_t* win_off, 
   }
   const int T = 1 + win_len / hop;
   const int acw = ctx.t.ac512;
-  if (ws_bytes < window_stage_ws_bytes(ctx, n_win, T)) {
+  WsCarve c(ws);
+  const WindowWs w = window_stage_ws(c, n_win, T);
+  if (ws_bytes < c.bytes()) {
     set_error("window stage: workspace too small");
     return -3;
   }
   const size_t F = (size_t)n_win * T;
-  char* q = static_cast<char*>(ws);
-  float* sdb = reinterpret_cast<float*>(q);
-  q += a256(F * 128 * sizeof(float));
-  float* fmax_ = reinterpret_cast<float*>(q);
-  q += a256(F * sizeof(float));
-  double* fen = reinterpret_cast<double*>(q);
 
   StftMelArgs s{};
   s.sig = sig;
@@ -384,9 +390,9 @@ int launch_window_stage(Context& ctx, const float* sig, const int64_t* win_off, 
   s.total_frames = (int64_t)F;
   s.active = active;
   s.hop = hop;
-  s.sdb = sdb;
-  s.frame_max = fmax_;
-  s.frame_energy = energy_out ? fen : nullptr;
+  s.sdb = w.sdb;
+  s.frame_max = w.fmax_;
+  s.frame_energy = energy_out ? w.fen : nullptr;
   if (win_chunk) {
     // a shared frame must see no right-edge padding of the window: t hop + n_fft / 2 <= win_len
     if (!chunk_tf_base || !peak_pitch || !peak_mag || !chunk_npk || tp_frames < 0 || tp_frames > T ||
@@ -407,9 +413,9 @@ int launch_window_stage(Context& ctx, const float* sig, const int64_t* win_off, 
   if (stft_done) NC_HIP(hipEventRecord(static_cast<hipEvent_t>(stft_done), st));
 
   WinTgArgs a;
-  a.sdb = sdb;
-  a.frame_max = fmax_;
-  a.frame_energy = energy_out ? fen : nullptr;
+  a.sdb = w.sdb;
+  a.frame_max = w.fmax_;
+  a.frame_energy = energy_out ? w.fen : nullptr;
   a.active = active;
   a.n_win = n_win;
   a.T = T;

@@ -12,7 +12,7 @@
 // correspondences, least-squares slope (np.polyfit deg 1) and median quality,
 // over every window of the job (the reference's n_windows has no upper limit).
 #include "nc_block.h"
-#include "nc_engine.h"
+#include "nc_launch.h"
 
 namespace nc {
 
