@@ -58,18 +58,6 @@ __host__ __device__ __forceinline__ size_t al16(size_t n) { return (n + 15) & ~(
 // its outstanding global loads/stores (which __syncthreads' fence would drain every block).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-#ifdef NC_BEAT_PROF
-#define NC_BEAT_T(k) \
-  do { __syncthreads(); if (threadIdx.x == 0) prof_t[k] = wall_clock64(); } while (0)
-#define NC_BEAT_DUMP() \
-  do { if (threadIdx.x == 0 && blockIdx.x == 0) printf("beatprof SMALL=%d N=%d P=%d: %ld %ld %ld %ld %ld %ld\n", (int)SMALL, N, Pi, \
-       (long)(prof_t[1]-prof_t[0]), (long)(prof_t[2]-prof_t[1]), (long)(prof_t[3]-prof_t[2]), (long)(prof_t[4]-prof_t[3]), \
-       (long)(prof_t[5]-prof_t[4]), (long)(prof_t[6]-prof_t[5])); } while (0)
-#else
-#define NC_BEAT_T(k) do {} while (0)
-#define NC_BEAT_DUMP() do {} while (0)
-#endif
-
 // beat_track's local score: the onset envelope (normalised) convolved with a Gaussian
 // window of 2P + 1 taps, exp(-0.5 ((k - P) 32 / P)^2), summed in ascending tap order
 __device__ __forceinline__ double beat_window(int k, int Pi, double P) {
@@ -120,9 +108,6 @@ __global__ __launch_bounds__(NT) void tempo_beat_kernel(BeatArgs a) {
   __shared__ double sel_med[2];
   __shared__ double dp_best[NT];
   __shared__ int dp_d[NT];
-#ifdef NC_BEAT_PROF
-  __shared__ long long prof_t[8];
-#endif
   const int s = blockIdx.x;
 
   if (a.active && !a.active[s]) {
@@ -171,7 +156,6 @@ __global__ __launch_bounds__(NT) void tempo_beat_kernel(BeatArgs a) {
   }
 
   // ------------------------------------------------------------ tempo: prior-weighted argmax
-  NC_BEAT_T(0);
   const double fs = (double)a.sr;
   const double start = a.prior_idx ? a.start_bpm[a.prior_idx[s]] : a.start_bpm[s];
   const double lstart = log2(start);
@@ -224,7 +208,6 @@ __global__ __launch_bounds__(NT) void tempo_beat_kernel(BeatArgs a) {
   const int Pi = (int)P;
 
   // ------------------------------------------------------------ normalise + local score
-  NC_BEAT_T(1);
   // Long sequences split this section over three launches (launch_tempo_beats): phase 1
   // stops after the normalised onset (meta in back[0..3]: P, -, -, ready), beat_localscore_kernel
   // fills ls[] across the chip, phase 2 starts from ls[].
@@ -273,7 +256,6 @@ __global__ __launch_bounds__(NT) void tempo_beat_kernel(BeatArgs a) {
   const int i0 = block_min_i<NT>(first, bs);
 
   // ------------------------------------------------------------ DP
-  NC_BEAT_T(2);
   const int dmin = (int)rint(P / 2.0);
   const int dmax = 2 * Pi;
   const double lP = log(P);
@@ -443,7 +425,6 @@ __global__ __launch_bounds__(NT) void tempo_beat_kernel(BeatArgs a) {
   __syncthreads();  // cum / back global stores (long sequences) visible to the whole workgroup
 
   // ------------------------------------------------------------ last beat
-  NC_BEAT_T(3);
   for (int i = threadIdx.x; i < N; i += NT) {
     const double x = cum[i];
     const bool left = i > 0 ? (x > cum[i - 1]) : false;
@@ -497,7 +478,6 @@ __global__ __launch_bounds__(NT) void tempo_beat_kernel(BeatArgs a) {
   }
 
   // ------------------------------------------------------------ backtrack
-  NC_BEAT_T(4);
   __syncthreads();
   for (int i = threadIdx.x; i < N; i += NT) marks[i] = 0;
   __syncthreads();
@@ -523,7 +503,6 @@ __global__ __launch_bounds__(NT) void tempo_beat_kernel(BeatArgs a) {
   __syncthreads();
 
   // ------------------------------------------------------------ trim (0.5 RMS of smoothed beat scores)
-  NC_BEAT_T(5);
   double thr3 = 0.0;
   if (a.trim) {
     double e2 = 0.0;
@@ -567,8 +546,6 @@ __global__ __launch_bounds__(NT) void tempo_beat_kernel(BeatArgs a) {
   if (threadIdx.x == 0) a.nbeats_out[s] = nkeep;
   if (a.beats_out)
     for (int j = threadIdx.x; j < nkeep; j += NT) a.beats_out[off + j] = back[kfirst + j];
-  NC_BEAT_T(6);
-  NC_BEAT_DUMP();
   (void)sh_int;
 }
 
@@ -660,8 +637,7 @@ int launch_tempo_beats(Context& ctx, BeatArgs a, int n_seq, int max_len, hipStre
     {
       KTimer kt_(ctx, "tempo_beat", st);
       a.span = kt_.span();
-      for (int rep = 0; rep < NC_PROBE_REPS(0); ++rep)
-        hipLaunchKernelGGL((tempo_beat_kernel<256, true>), dim3(n_seq), dim3(256), small_lds, st, a);
+      hipLaunchKernelGGL((tempo_beat_kernel<256, true>), dim3(n_seq), dim3(256), small_lds, st, a);
     }
   } else {
     if (!a.ws_ls || !a.ws_cum || !a.ws_back || !a.ws_marks) {

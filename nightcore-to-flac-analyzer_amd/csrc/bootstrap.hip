@@ -610,19 +610,8 @@ size_t bootstrap_job_bytes(int cap, int n_boot) {
   return c.bytes();
 }
 
-#ifndef NC_PROBE_SKIP_BOOT
-#define NC_PROBE_SKIP_BOOT 0  // timing probe (outputs wrong): one tiny launch writing ratio 1 instead
-#endif
-__global__ void boot_probe_fill_kernel(BootArgs a, int n_jobs) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < n_jobs) a.point_out[j] = a.lo_out[j] = a.hi_out[j] = 1.0;
-}
 int launch_bootstrap(const BootArgs& a, int n_jobs, hipStream_t st) {
   if (n_jobs <= 0) return 0;
-  if (NC_PROBE_SKIP_BOOT) {
-    hipLaunchKernelGGL(boot_probe_fill_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, st, a, n_jobs);
-    return 0;
-  }
   if (a.n_boot > 2048 || a.n_boot < 1) {
     set_error("bootstrap: n_boot must be in [1, 2048]");
     return -2;
@@ -633,8 +622,7 @@ int launch_bootstrap(const BootArgs& a, int n_jobs, hipStream_t st) {
   hipLaunchKernelGGL(bootstrap_rejscan_kernel, dim3(SCAN_WG, n_jobs), dim3(BT), 0, st, a);
   hipLaunchKernelGGL(bootstrap_walk_kernel, dim3(n_jobs), dim3(BT), 0, st, a);
   hipLaunchKernelGGL(bootstrap_draw_kernel<true>, gd, dim3(BD), 0, st, a);
-  for (int rep = 0; rep < NC_PROBE_REPS(1); ++rep)
-    hipLaunchKernelGGL(bootstrap_finish_kernel, dim3(n_jobs), dim3(BT), 0, st, a);
+  hipLaunchKernelGGL(bootstrap_finish_kernel, dim3(n_jobs), dim3(BT), 0, st, a);
   NC_HIP(hipGetLastError());
   return 0;
 }

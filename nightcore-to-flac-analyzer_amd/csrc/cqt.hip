@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void chroma_plan_kernel(const int64_t* chunk_l
 // values as 7 aligned float4 LDS loads and the centre values as one.  Measured: 1.19 ->
 // 0.77 ms per bench step (isolated); in round 2, 512-output tiles (26 KB LDS) were as fast
 // alone but co-resided worse with stft_mel on the other stream (step 14.5 -> 15.5 ms; 256
-// (14 KB) gave 14.1 ms) -- see D3_TILE for round 4.
+// (14 KB) gave 14.1 ms) -- see D3_T for round 4.
 // Round 4, with stft_mel's LDS reserve keeping this kernel off the STFT's CUs: 128 / 256 / 512 /
 // 768 / 1024 outputs per workgroup (256 threads) ran 1.40 / 0.98 / 0.82 / 0.94 / 1.01 ms per step
 // isolated (six, four and three workgroups per CU past 512 by LDS), the pipelined step the same
@@ -113,14 +113,10 @@ __global__ __launch_bounds__(256) void chroma_plan_kernel(const int64_t* chunk_l
 // pass is exactly two rounds of the 256 threads (4 T + 144 = 2048 values, 512 quads; at 512 it
 // was 548 quads, a third round for 36 threads) and level 2 one (250 quads): 215.0 -> 201.2 us
 // per 224 chunks, bit-identical (profiles/r5_decimate_476.txt).  Launched twice in the pipelined
-// step (NC_PROBE_TWICE), decimate3 adds 0.6-0.75 ms per step: it is on the step's critical path
-#ifndef D3_TILE
-#define D3_TILE 476
-#endif
-#ifndef D3_NT
-#define D3_NT 256  // threads per decimate3 workgroup
-#endif
-constexpr int D3_T = D3_TILE;           // level-(base + 3) outputs per decimate3 workgroup
+// step (profiles/r5_twice_probe.txt), decimate3 adds 0.6-0.75 ms per step: it is on the step's
+// critical path
+constexpr int D3_T = 476;               // level-(base + 3) outputs per decimate3 workgroup
+constexpr int D3_NT = 256;              // threads per decimate3 workgroup
 static_assert(D3_T % 4 == 0 && D3_T >= 256, "quads per level; xmax slots are spaced 256 apart");
 constexpr int D3_N1 = 4 * D3_T + 144;  // level base+1 values computed (from 4 m0 - 72)
 constexpr int D3_N2 = 2 * D3_T + 48;   // level base+2 values computed (from 2 m0 - 24)
@@ -617,15 +613,10 @@ constexpr int CM_RT = CM_FR / 16;                  // row tiles per wave
 // (twelve waves) per CU instead of two at 78 KB: 343.0 -> 326.5 us per 224 chunks, bit-identical;
 // 32 frames with the pads (two per CU) 381.2, 64 frames swizzled 348.5, 64 unpadded (bank
 // conflicts) 345.3 (profiles/r5_cqt_high_tiles.txt)
-#ifndef CH_FR_
-#define CH_FR_ 32
-#endif
-#ifndef CH_MINB_
-#define CH_MINB_ 3
-#endif
-constexpr int CH_FR = CH_FR_;                      // frames per cqt_mfma_kernel workgroup tile
+constexpr int CH_FR = 32;                          // frames per cqt_mfma_kernel workgroup tile
+constexpr int CH_MINB = 3;                         // its workgroups per CU (launch bound)
 constexpr int CH_RT = CH_FR / 16;                  // its row tiles per wave
-static_assert(CH_RT == 2 || CH_RT == 4, "tile rows");
+static_assert(CH_RT == 2, "tile rows");
 constexpr int CM_KS = kCqtNfft / 32;               // k-steps of 32 taps
 constexpr int CM_NT = 5;                           // column tiles (72 of 80 columns used)
 constexpr int CM_R = 2;                            // filter-slice ring slots
@@ -641,33 +632,22 @@ typedef unsigned cm_u4 __attribute__((ext_vector_type(4)));
 // s_waitcnt immediate for vmcnt(n) alone (vmcnt [3:0] + [15:14]; expcnt, lgkmcnt at maximum)
 __host__ __device__ constexpr int cm_vmcnt(int n) { return (n & 15) | ((n >> 4) << 14) | 0x70 | 0xf00; }
 
-// LDS images: span 63 hop + 1024 samples as f16 hi then lo, with 16 halves of padding after
-// every hop samples when hop >= 32 (row r starts at r (hop + pad)); a row's 8-sample piece
-// never straddles a pad.  ds_read_b128 serves a wave in the lane groups {0-3, 12-15, 20-27},
-// {4-11, 16-19, 28-31}, ... (MI355X_MICROARCH.md, LDS table): a group holds 8 rows at one k
-// offset and 8 rows at the next, and with these pads its 16 pieces fall on distinct banks for
-// every octave and k-step (the round-2 pads, 8 halves when hop >= 16, gave 2-way conflicts
-// for octaves 3-5)
+// LDS images: span (CH_FR - 1) hop + 1024 samples as f16 hi then lo.  ds_read_b128 serves a
+// wave in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... (MI355X_MICROARCH.md,
+// LDS table): a group holds 8 rows at one k offset and 8 rows at the next.  No pads; instead
+// 16-byte piece P of a hop-64 / hop-32 image sits at P ^ cm_swz(P), an XOR of its low four bits
+// keyed by its 256-byte block (conflict-free for every fragment read by that bank model,
+// tests/test_lds_layout_cpu.py); hop 16 and 8 are conflict-free as they are.  (Until round 5:
+// 16 halves of padding after every hop samples when hop >= 32, profiles/r5_cqt_high_tiles.txt)
 __host__ __device__ constexpr int cm_hop(int o) { return 512 >> o; }
-#ifndef CH_PAD_
-#define CH_PAD_ 16
-#endif
-// CH_SWZ_: no pads; instead 16-byte piece P of a hop-64 / hop-32 image sits at P ^ cm_swz(P),
-// an XOR of its low four bits keyed by its 256-byte block (conflict-free for every fragment
-// read by the bank model above, tests/test_lds_layout_cpu.py); hop 16 and 8 are conflict-free
-// unpadded
-#ifndef CH_SWZ_
-#define CH_SWZ_ 1
-#endif
-__host__ __device__ constexpr int cm_pad(int o) { return cm_hop(o) >= 32 && !CH_SWZ_ ? CH_PAD_ : 0; }
 // (key table, block-index mask) of octave o's swizzle: h[(P >> 4) & m] = (K >> 4 ((P >> 4) & m)) & 15
-__host__ __device__ constexpr unsigned cm_swz_k(int o) { return !CH_SWZ_ ? 0u : cm_hop(o) == 64 ? 0xC638u : cm_hop(o) == 32 ? 0xF8u : 0u; }
+__host__ __device__ constexpr unsigned cm_swz_k(int o) { return cm_hop(o) == 64 ? 0xC638u : cm_hop(o) == 32 ? 0xF8u : 0u; }
 __host__ __device__ constexpr int cm_swz_m(int o) { return cm_hop(o) == 64 ? 3 : 1; }
 __host__ __device__ __forceinline__ int cm_phys(int P, unsigned K, int m) { return P ^ (int)((K >> (((P >> 4) & m) << 2)) & 15u); }
 __host__ __device__ constexpr int cm_span(int o) { return (CH_FR - 1) * cm_hop(o) + kCqtNfft; }
 __host__ __device__ constexpr int cm_img(int o) {  // halves per hi (or lo) image, 16-byte multiple
   // (whole 256-byte blocks when swizzled: a piece of the last block may move anywhere in it)
-  return cm_swz_k(o) ? (cm_span(o) + 127) & ~127 : (cm_span(o) + (cm_span(o) / cm_hop(o)) * cm_pad(o) + 7) & ~7;
+  return cm_swz_k(o) ? (cm_span(o) + 127) & ~127 : (cm_span(o) + 7) & ~7;
 }
 __host__ __device__ constexpr int cm_aoff(int o) {  // byte offset of octave o's image pair
   return o <= CM_LO ? 0 : cm_aoff(o - 1) + 4 * cm_img(o - 1);
@@ -745,7 +725,36 @@ __device__ __forceinline__ void cm_split(const float (&v)[8], float s, cm_half8&
   lo = __builtin_bit_cast(cm_half8, l);
 }
 
-__global__ __launch_bounds__(CM_NTH, CH_MINB_) void cqt_mfma_kernel(CqmArgs a) {
+// ---- shared by cqt_mfma_kernel and cqt_low_tile (their k-step schedules differ and stay apart)
+// Filter slice ks (CM_NT * 2 pieces of 64 uint4) of bsrc into ring slot `slot` of sB by LDS-DMA, NP
+// pieces by each of the workgroup's NW waves.  (Arguments by reference, as the lambdas this replaces
+// captured them: by value the compiler forms the source addresses differently, on the VALU)
+template <int NW, int NP>
+__device__ __forceinline__ void cm_fetch_slice(const uint4* const& bsrc, int ks, uint4* const& sB, int slot,
+                                               const int& wave, const int& lane) {
+#pragma unroll
+  for (int q = 0; q < NP; ++q) {
+    int i = wave + NW * q;
+    if (i >= CM_NT * 2) i = wave;  // duplicate of this wave's first piece (same bytes, same place)
+    cm_dma16(bsrc + ks * CM_SLICE + i * 64 + lane, sB + slot * CM_SLICE + i * 64);
+  }
+}
+
+// Column tile nt of one k-step: hh, hl, lh per row tile into acc[rt][nt]
+template <int RT>
+__device__ __forceinline__ void cm_tile(cm_f4 (&acc)[RT][CM_NT], int nt, const cm_half8 (&ah)[RT],
+                                        const cm_half8 (&al)[RT], const cm_u4 (&b)[2]) {
+  const cm_half8 bh = __builtin_bit_cast(cm_half8, b[0]);
+  const cm_half8 bl = __builtin_bit_cast(cm_half8, b[1]);
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+    acc[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt], bh, acc[rt][nt], 0, 0, 0);
+    acc[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt], bl, acc[rt][nt], 0, 0, 0);
+    acc[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rt], bh, acc[rt][nt], 0, 0, 0);
+  }
+}
+
+__global__ __launch_bounds__(CM_NTH, CH_MINB) void cqt_mfma_kernel(CqmArgs a) {
   const Span span_(a.span);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint4* sB = reinterpret_cast<uint4*>(smem);  // [CM_R][CM_SLICE]
@@ -765,14 +774,7 @@ __global__ __launch_bounds__(CM_NTH, CH_MINB_) void cqt_mfma_kernel(CqmArgs a) {
   const int nfr = min(CH_FR, T - t0);
   const uint4* bsrc = a.bfrag + (size_t)ti * (CM_KS * CM_SLICE);
   // the first filter slice is in flight while the image is built
-  auto fetch_slice = [&](int ks) {
-#pragma unroll
-    for (int q = 0; q < CM_GQ; ++q) {
-      int i = wave + CM_NW * q;
-      if (i >= CM_NT * 2) i = wave;  // duplicate of this wave's first piece (same bytes, same place)
-      cm_dma16(bsrc + ks * CM_SLICE + i * 64 + lane, sB + (ks % CM_R) * CM_SLICE + i * 64);
-    }
-  };
+  auto fetch_slice = [&](int ks) { cm_fetch_slice<CM_NW, CM_GQ>(bsrc, ks, sB, ks % CM_R, wave, lane); };
   fetch_slice(0);
 
   // this wave's octave: rows t0 .. t0 + 63, row t at sample t hop - 512
@@ -786,7 +788,6 @@ __global__ __launch_bounds__(CM_NTH, CH_MINB_) void cqt_mfma_kernel(CqmArgs a) {
 
   // the span, split once (rows past T - 1 read real or zero samples and are discarded)
   constexpr int aoffs[8] = {cm_aoff(0), cm_aoff(1), cm_aoff(2), cm_aoff(3), cm_aoff(4), cm_aoff(5), cm_aoff(6), cm_aoff(7)};
-  const int pad = cm_pad(oct);
   const int img = cm_img(oct);
   constexpr unsigned swk[8] = {cm_swz_k(0), cm_swz_k(1), cm_swz_k(2), cm_swz_k(3), cm_swz_k(4), cm_swz_k(5), cm_swz_k(6), cm_swz_k(7)};
   const unsigned sk = swk[oct];
@@ -810,7 +811,7 @@ __global__ __launch_bounds__(CM_NTH, CH_MINB_) void cqt_mfma_kernel(CqmArgs a) {
         const float v[8] = {u[k][0].x, u[k][0].y, u[k][0].z, u[k][0].w, u[k][1].x, u[k][1].y, u[k][1].z, u[k][1].w};
         cm_half8 h, l;
         cm_split(v, sx, h, l);
-        const int pos = CH_SWZ_ ? 8 * cm_phys(i, sk, sm) : 8 * i + (8 * i / hop) * pad;
+        const int pos = 8 * cm_phys(i, sk, sm);
         *reinterpret_cast<cm_half8*>(aimg + pos) = h;
         *reinterpret_cast<cm_half8*>(aimg + img + pos) = l;
       }
@@ -832,15 +833,14 @@ __global__ __launch_bounds__(CM_NTH, CH_MINB_) void cqt_mfma_kernel(CqmArgs a) {
     }
     cm_half8 h, l;
     cm_split(v, sx, h, l);
-    const int pos = CH_SWZ_ ? 8 * cm_phys(i, sk, sm) : 8 * i + (8 * i / hop) * pad;
+    const int pos = 8 * cm_phys(i, sk, sm);
     *reinterpret_cast<cm_half8*>(aimg + pos) = h;
     *reinterpret_cast<cm_half8*>(aimg + img + pos) = l;
   }
   int abase[CH_RT];
 #pragma unroll
   for (int rt = 0; rt < CH_RT; ++rt)
-    abase[rt] = CH_SWZ_ ? ((16 * rt + (lane & 15)) * hop + kq) / 8  // the fragment's first piece
-                        : (16 * rt + (lane & 15)) * (hop + pad) + kq + (kq / hop) * pad;
+    abase[rt] = ((16 * rt + (lane & 15)) * hop + kq) / 8;  // the fragment's first piece
 
   cm_f4 acc[CH_RT][CM_NT];
 #pragma unroll
@@ -860,44 +860,29 @@ __global__ __launch_bounds__(CM_NTH, CH_MINB_) void cqt_mfma_kernel(CqmArgs a) {
     // A fragments of k-step ks (this wave's own image: written by this wave only, and LDS
     // operations of one wave complete in order, so no barrier guards them), then the B
     // fragments two column tiles ahead of their MFMAs
-    const int kt = 32 * ks + (32 * ks / hop) * pad;
     const uint32_t sbl = lds_addr(sB + (ks % CM_R) * CM_SLICE + lane);
     cm_u4 a4[CH_RT], l4[CH_RT], b[CM_NT][2];
     static_assert(CM_NT == 5, "fragment schedule");
 #pragma unroll
     for (int rt = 0; rt < CH_RT; ++rt)
-      cm_rd<0>(a4[rt], lds_addr(aimg + (CH_SWZ_ ? 8 * cm_phys(abase[rt] + 4 * ks, sk, sm) : abase[rt] + kt)));
+      cm_rd<0>(a4[rt], lds_addr(aimg + 8 * cm_phys(abase[rt] + 4 * ks, sk, sm)));
 #pragma unroll
     for (int rt = 0; rt < CH_RT; ++rt)
-      cm_rd<0>(l4[rt], lds_addr(aimg + img + (CH_SWZ_ ? 8 * cm_phys(abase[rt] + 4 * ks, sk, sm) : abase[rt] + kt)));
+      cm_rd<0>(l4[rt], lds_addr(aimg + img + 8 * cm_phys(abase[rt] + 4 * ks, sk, sm)));
     cm_rd<0 * 1024>(b[0][0], sbl);
     cm_rd<1 * 1024>(b[0][1], sbl);
     cm_rd<2 * 1024>(b[1][0], sbl);
     cm_rd<3 * 1024>(b[1][1], sbl);
     cm_rd<4 * 1024>(b[2][0], sbl);
     cm_rd<5 * 1024>(b[2][1], sbl);
-    if constexpr (CH_RT == 4) {
-      cm_wait<4>(a4[0], a4[1], a4[2], a4[3]);  // A + tile 0 landed; tiles 1, 2 in flight
-      cm_wait<4>(l4[0], l4[1], l4[2], l4[3]);
-    } else {
-      cm_wait<4>(a4[0], a4[1], l4[0], l4[1]);
-    }
+    cm_wait<4>(a4[0], a4[1], l4[0], l4[1]);  // A + tile 0 landed; tiles 1, 2 in flight
     cm_half8 ah[CH_RT], al[CH_RT];
 #pragma unroll
     for (int rt = 0; rt < CH_RT; ++rt) {
       ah[rt] = __builtin_bit_cast(cm_half8, a4[rt]);
       al[rt] = __builtin_bit_cast(cm_half8, l4[rt]);
     }
-    auto tile = [&](int nt) {
-      const cm_half8 bh = __builtin_bit_cast(cm_half8, b[nt][0]);
-      const cm_half8 bl = __builtin_bit_cast(cm_half8, b[nt][1]);
-#pragma unroll
-      for (int rt = 0; rt < CH_RT; ++rt) {
-        acc[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt], bh, acc[rt][nt], 0, 0, 0);
-        acc[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt], bl, acc[rt][nt], 0, 0, 0);
-        acc[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rt], bh, acc[rt][nt], 0, 0, 0);
-      }
-    };
+    auto tile = [&](int nt) { cm_tile<CH_RT>(acc, nt, ah, al, b[nt]); };
     cm_wait<4>(b[0][0], b[0][1]);
     tile(0);
     cm_rd<6 * 1024>(b[3][0], sbl);
@@ -970,8 +955,8 @@ __global__ __launch_bounds__(CM_NTH, CH_MINB_) void cqt_mfma_kernel(CqmArgs a) {
 //    and the reverse, a cold register load then 4 hot LDS-DMA pieces: 0 stale of 3.4e8 lane-trials
 //    each, profiles/r6_vmcnt_order.txt), as MI355X_MICROARCH.md states.  (Round 5 had blamed out-of-
 //    order retirement for NaNs from a counted wait on the block loads; the block wait stays
-//    vmcnt(0).  C2_SAFE_=1, vmcnt(0) wherever a block load is younger than the slice, measured
-//    the same: 353.3 against 352.7 us per 224 chunks, profiles/r6_var_bench.txt);
+//    vmcnt(0).  vmcnt(0) wherever a block load is younger than the slice measured the same:
+//    353.3 against 352.7 us per 224 chunks, profiles/r6_var_bench.txt);
 //  * block loads are dword-aligned dwordx4 (gfx950 serves unaligned global loads), so an
 //    unaligned chunk issues the same instructions; an edge tile loads clamped pieces and zeroes
 //    the samples outside the signal when it splits.
@@ -982,33 +967,17 @@ __global__ __launch_bounds__(CM_NTH, CH_MINB_) void cqt_mfma_kernel(CqmArgs a) {
 // 4 tiles per workgroup and a 4-slot ring 480.9 (16 tile slots for 13.5 tiles of work), 2 tiles
 // and a 3-slot ring 416.9 (three workgroups per CU), 2 tiles and 2 slots 358.6.  Probes of the
 // last (outputs wrong): no barrier 338.6, no MFMA 259.3, no split 297.5.
-// tile geometry knobs (probes; the defaults are the kernel described above).  32-frame tiles, four
-// per workgroup (-DC2_FR_=32 -DC2_NW_=4 -DC2_MINB_=3: three waves per SIMD, 168 VGPRs, spills only
-// in octave 0's edge instance), bit-identical, round 5, us per 224 chunks (profiles/
-// r5_cqt_low_fr32.txt): all three octaves 353.5 against 344.1; octave 0 alone 186.9 against 172.2,
-// octave 1 alone 117.7 against 131.3 (134 VGPRs).  Two waves per SIMD (-DC2_MINB_=2) 396.4.  A
-// mixed launch (octave 0 at 64 frames, 1-2 at 32) needs two kernels and gives up the octaves'
-// overlap inside one launch (all three 328-344 against 424 for the three alone): not built
-#ifndef C2_FR_
-#define C2_FR_ 64
-#endif
-#ifndef C2_NW_
-#define C2_NW_ 2
-#endif
-#ifndef C2_MINB_
-#define C2_MINB_ 2
-#endif
-constexpr int C2_FR = C2_FR_;                             // frames per tile (one wave)
+// 32-frame tiles, four per workgroup, three waves per SIMD (round 5, bit-identical): all three
+// octaves 353.5 against 344.1 us per 224 chunks (profiles/r5_cqt_low_fr32.txt)
+constexpr int C2_FR = 64;                                 // frames per tile (one wave)
 constexpr int C2_RT = C2_FR / 16;                         // 16-row tiles per wave
-static_assert(C2_RT == 2 || C2_RT == 4, "tile rows");
-constexpr int C2_NW = C2_NW_;                             // tiles (waves) per workgroup
+static_assert(C2_RT == 4, "tile rows");
+constexpr int C2_NW = 2;                                  // tiles (waves) per workgroup
+constexpr int C2_MINB = 2;                                // workgroups per CU (launch bound)
 constexpr int C2_R = 2;                                   // filter ring slots
 constexpr int C2_D = C2_R - 1;                            // slices requested ahead of the step that reads them
 constexpr int C2_PS = (CM_NT * 2 + C2_NW - 1) / C2_NW;    // slice DMA pieces per wave per step
-#ifndef C2_NRP_
-#define C2_NRP_ (C2_FR + 8)
-#endif
-constexpr int C2_NRP = C2_NRP_;                           // image rows per wave (>= C2_FR + M - 1)
+constexpr int C2_NRP = C2_FR + 8;                         // image rows per wave (>= C2_FR + M - 1)
 constexpr int C2_IMG = C2_NRP * 64;                       // bytes of one hi (or lo) image
 constexpr int C2_RING = C2_R * CM_SLICE * 16;
 constexpr int C2_NU = (C2_NRP * 4 + 63) / 64;             // staging rounds (8-sample units per lane)
@@ -1030,18 +999,12 @@ __device__ __forceinline__ void c2_vmwait() {
 }
 template <int N>
 __device__ __forceinline__ void c2_vmwait_st(cm_u4 (&st)[C2_NL]) {
-  static_assert(C2_NL == 10 || C2_NL == 6, "staging registers");
-  if constexpr (C2_NL == 10)
-    asm volatile("s_waitcnt vmcnt(%10)"
-                 : "+v"(st[0]), "+v"(st[1]), "+v"(st[2]), "+v"(st[3]), "+v"(st[4]), "+v"(st[5]), "+v"(st[6]),
-                   "+v"(st[7]), "+v"(st[8]), "+v"(st[9])
-                 : "i"(N)
-                 : "memory");
-  else
-    asm volatile("s_waitcnt vmcnt(%6)"
-                 : "+v"(st[0]), "+v"(st[1]), "+v"(st[2]), "+v"(st[3]), "+v"(st[4]), "+v"(st[5])
-                 : "i"(N)
-                 : "memory");
+  static_assert(C2_NL == 10, "staging registers");
+  asm volatile("s_waitcnt vmcnt(%10)"
+               : "+v"(st[0]), "+v"(st[1]), "+v"(st[2]), "+v"(st[3]), "+v"(st[4]), "+v"(st[5]), "+v"(st[6]),
+                 "+v"(st[7]), "+v"(st[8]), "+v"(st[9])
+               : "i"(N)
+               : "memory");
 }
 
 template <int OCT>
@@ -1069,28 +1032,11 @@ struct C2 {
   }
 };
 
-// vmcnt(younger(q, last)): retires this wave's pieces of slice n (this step's slot).
-// C2_SAFE_=1 (probe): vmcnt(0) wherever a block load is younger than the slice
-#ifndef C2_SAFE_
-#define C2_SAFE_ 0
-#endif
-// C2_NOBW_=1 (timing probe, outputs wrong): octave C2_NOBW_OCT_ splits its next block without
-// waiting for its loads, i.e. the cost of the block loads' exposed latency
-#ifndef C2_NOBW_
-#define C2_NOBW_ 0
-#endif
-#ifndef C2_NOBW_OCT_
-#define C2_NOBW_OCT_ 0
-#endif
+// vmcnt(younger(q, last)): retires this wave's pieces of slice n (this step's slot)
 template <int OCT, int Q>
 __device__ __forceinline__ void c2_wait_slice(bool last) {
-  if (C2_SAFE_) {
-    if (last) c2_vmwait<C2<OCT>::staged(Q, 1, true) ? 0 : C2<OCT>::younger(Q, true)>();
-    else c2_vmwait<C2<OCT>::staged(Q, 1, false) ? 0 : C2<OCT>::younger(Q, false)>();
-  } else {
-    if (last) c2_vmwait<C2<OCT>::younger(Q, true)>();
-    else c2_vmwait<C2<OCT>::younger(Q, false)>();
-  }
+  if (last) c2_vmwait<C2<OCT>::younger(Q, true)>();
+  else c2_vmwait<C2<OCT>::younger(Q, false)>();
 }
 
 // Block g of this wave's tile into registers: 8-sample unit u = 64 k + lane is row min(u / 4,
@@ -1187,14 +1133,7 @@ __device__ __forceinline__ void cqt_low_tile(const CqmArgs& a, int bx, int c) {
   char* img = smem + C2_RING + wave * (2 * C2_IMG);
   const float sx = ldexpf(1.0f, ex);
   auto kstep = [](int n) { return n / M + G * (n % M); };
-  auto fetch_slice = [&](int n) {
-#pragma unroll
-    for (int j = 0; j < C2_PS; ++j) {
-      int i = wave + C2_NW * j;
-      if (i >= CM_NT * 2) i = wave;  // duplicate of this wave's first piece (same bytes, same place)
-      cm_dma16(bsrc + kstep(n) * CM_SLICE + i * 64 + lane, sB + (n % C2_R) * CM_SLICE + i * 64);
-    }
-  };
+  auto fetch_slice = [&](int n) { cm_fetch_slice<C2_NW, C2_PS>(bsrc, kstep(n), sB, n % C2_R, wave, lane); };
 
   // prologue: slices 0-2 in flight, block 0 split, block 1 requested at step 0
   for (int d = 0; d < C2_D; ++d) fetch_slice(d);
@@ -1235,28 +1174,15 @@ __device__ __forceinline__ void cqt_low_tile(const CqmArgs& a, int bx, int c) {
       cm_rd<1 * 1024>(b[0][1], sbl);
       cm_rd<2 * 1024>(b[1][0], sbl);
       cm_rd<3 * 1024>(b[1][1], sbl);
-      if constexpr (C2_RT == 4) {
-        cm_wait<4>(ah4[0], ah4[1], ah4[2], ah4[3]);  // A + tile 0 landed; tile 1 in flight
-        cm_wait<4>(al4[0], al4[1], al4[2], al4[3]);
-      } else {
-        cm_wait<4>(ah4[0], ah4[1], al4[0], al4[1]);
-      }
+      cm_wait<4>(ah4[0], ah4[1], ah4[2], ah4[3]);  // A + tile 0 landed; tile 1 in flight
+      cm_wait<4>(al4[0], al4[1], al4[2], al4[3]);
       cm_half8 ah[C2_RT], al[C2_RT];
 #pragma unroll
       for (int rt = 0; rt < C2_RT; ++rt) {
         ah[rt] = __builtin_bit_cast(cm_half8, ah4[rt]);
         al[rt] = __builtin_bit_cast(cm_half8, al4[rt]);
       }
-      auto tile = [&](int nt) {
-        const cm_half8 bh = __builtin_bit_cast(cm_half8, b[nt][0]);
-        const cm_half8 bl = __builtin_bit_cast(cm_half8, b[nt][1]);
-#pragma unroll
-        for (int rt = 0; rt < C2_RT; ++rt) {
-          acc[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt], bh, acc[rt][nt], 0, 0, 0);
-          acc[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt], bl, acc[rt][nt], 0, 0, 0);
-          acc[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rt], bh, acc[rt][nt], 0, 0, 0);
-        }
-      };
+      auto tile = [&](int nt) { cm_tile<C2_RT>(acc, nt, ah, al, b[nt]); };
       // the MFMA cluster at priority 1: the partner wave on the SIMD (another workgroup's tile)
       // takes the VALU / LDS slots around it (round 5: 347.7 -> 339.4 us per 224 chunks, the same
       // pair on cqt_mfma_kernel 328.6 -> 332.1, not kept there; profiles/r5_cqt_sched_variants.txt)
@@ -1284,7 +1210,7 @@ __device__ __forceinline__ void cqt_low_tile(const CqmArgs& a, int bx, int c) {
       // group g is done (their registers were consumed above).  vmcnt(0), not a count: younger
       // slice pieces can retire before the block loads (header).  Splitting after the first or
       // third column tile of the step instead: 351.4 / 350.2 against 347.7 us (round 5)
-      if (!(C2_NOBW_ && OCT == C2_NOBW_OCT_)) c2_vmwait_st<0>(st);
+      c2_vmwait_st<0>(st);
       if (active) c2_split<OCT>(st, img, sx, s0, g + 1, Ly, EDGE, lane);
     }
   };
@@ -1293,7 +1219,6 @@ __device__ __forceinline__ void cqt_low_tile(const CqmArgs& a, int bx, int c) {
     const bool last = g == G - 1;
     static_for<M>([&](auto qc) { step(qc, g, last); });
   }
-  if (C2_NOBW_) c2_vmwait<0>();  // (probe) the skipped block waits' loads land before the epilogue
   if (!active) return;
   const int nrow = min(C2_FR, T - t0);
   float* mg = reinterpret_cast<float*>(img);  // [C2_FR][36] rows over this wave's own images
@@ -1328,48 +1253,23 @@ __device__ __forceinline__ void cqt_low_tile(const CqmArgs& a, int bx, int c) {
   }
 }
 
-// CQL_ONLY (timing probe, outputs wrong): >= 0 launches only that octave; 3 (with -DC2_NRP_=80)
-// runs octave 3 through this kernel's structure.  Round 5, rotated timer, us per 224 chunks alone
-// (profiles/r5_cqt_low_octaves.txt): octave 0 175.2, 1 133.0, 2 116.0, 3 107.7, all three 328.0:
-// octave 0 (two k-steps per block, the block loads one k-step ahead of their split) costs most.
-// Interleaving the octaves in dispatch order (each XCD's consecutive workgroups the three octaves
-// of one tile pair) ran 359.6 -> 392.8 (not kept)
-#ifndef CQL_ONLY
-#define CQL_ONLY -1
-#endif
-// C2_XCD_=1 (probe): workgroups dispatched to one XCD (linear ids b, b + 8, ...; placement
-// round-robin, speed only) take consecutive (tile pair, chunk, octave) items, so the tiles of one
-// (chunk, octave) and their tuning's 320 KB filter set share one L2 instead of seven
-#ifndef C2_XCD_
-#define C2_XCD_ 0
-#endif
-__global__ __launch_bounds__(C2_NW * 64, C2_MINB_) void cqt_mfma_low_kernel(CqmArgs a) {
-  unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  if (C2_XCD_) {
-    const unsigned X = gridDim.x, Y = gridDim.y, nb = X * Y * gridDim.z;
-    const unsigned b = bx + X * (by + Y * bz), xcd = b & 7, i = b >> 3, q = nb >> 3, rem = nb & 7;
-    const unsigned w = xcd < rem ? xcd * (q + 1) + i : rem * (q + 1) + (xcd - rem) * q + i;
-    bx = w % X;
-    by = (w / X) % Y;
-    bz = w / (X * Y);
-  }
-  const unsigned oz = CQL_ONLY >= 0 ? (unsigned)CQL_ONLY : bz;
-  if (oz == 0) {
+// Round 5, rotated timer, us per 224 chunks, each octave launched alone (profiles/
+// r5_cqt_low_octaves.txt): octave 0 175.2, 1 133.0, 2 116.0, all three 328.0: octave 0 (two
+// k-steps per block, the block loads one k-step ahead of their split) costs most.  Interleaving
+// the octaves in dispatch order (each XCD's consecutive workgroups the three octaves of one tile
+// pair) ran 359.6 -> 392.8 (not kept)
+__global__ __launch_bounds__(C2_NW * 64, C2_MINB) void cqt_mfma_low_kernel(CqmArgs a) {
+  const unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+  if (bz == 0) {
     cqt_low_tile<0, false>(a, bx, by);
     cqt_low_tile<0, true>(a, bx, by);
-  } else if (oz == 1) {
+  } else if (bz == 1) {
     cqt_low_tile<1, false>(a, bx, by);
     cqt_low_tile<1, true>(a, bx, by);
-  } else if (CQL_ONLY != 3) {
+  } else {
     cqt_low_tile<2, false>(a, bx, by);
     cqt_low_tile<2, true>(a, bx, by);
   }
-#if CQL_ONLY == 3
-  else {
-    cqt_low_tile<3, false>(a, bx, by);
-    cqt_low_tile<3, true>(a, bx, by);
-  }
-#endif
 }
 
 // Per (chunk, 64-frame tile): chroma = the 7 octave partial rows summed (ascending bins),
@@ -1541,7 +1441,7 @@ int chroma_ws_layout_query(int n, int64_t total_len, int64_t* out, int cap) {
   out[k++] = kEntries;
   for (int i = 0; i < CS_HEAD; ++i) out[k++] = (int64_t)l.off[i];
   out[k++] = (int64_t)l.end;
-  out[k++] = D3_TILE;
+  out[k++] = D3_T;
   out[k++] = kPeakSlots;
   out[k++] = CH_FR;
   out[k++] = C2_FR;
@@ -1600,9 +1500,8 @@ int launch_chroma_mean(Context& ctx, const float* sig, const int64_t* chunk_off,
       KTimer kt_(ctx, "decimate", st);
       D3Taps taps;
       std::copy(ctx.t.halfband_f32, ctx.t.halfband_f32 + 2 * kHalfbandK + 1, taps.h);
-      for (int rep = 0; rep < NC_PROBE_REPS(3); ++rep)
-        hipLaunchKernelGGL(decimate3_kernel, grid, dim3(D3_NT), 0, st, sig, chunk_off, w.oct_off, w.oct_len, w.ws_oct,
-                           base, taps, w.xmax, kt_.span());
+      hipLaunchKernelGGL(decimate3_kernel, grid, dim3(D3_NT), 0, st, sig, chunk_off, w.oct_off, w.oct_len, w.ws_oct,
+                         base, taps, w.xmax, kt_.span());
     }
   }
   PeakArgs pa;
@@ -1665,16 +1564,14 @@ int launch_chroma_mean(Context& ctx, const float* sig, const int64_t* chunk_off,
     KTimer kt_(ctx, "cqt_low", st);
     ma.span = kt_.span();
     const int ntl = (int)((1 + max_chunk_len / 512 + C2_FR - 1) / C2_FR);
-    const dim3 lg((unsigned)((ntl + C2_NW - 1) / C2_NW), (unsigned)n, CQL_ONLY >= 0 ? 1u : 3u);
-    for (int rep = 0; rep < NC_PROBE_REPS(4); ++rep)
-      hipLaunchKernelGGL(cqt_mfma_low_kernel, lg, dim3(C2_NW * 64), cql_lds_bytes(), st, ma);
+    const dim3 lg((unsigned)((ntl + C2_NW - 1) / C2_NW), (unsigned)n, 3u);
+    hipLaunchKernelGGL(cqt_mfma_low_kernel, lg, dim3(C2_NW * 64), cql_lds_bytes(), st, ma);
   }
   {
     KTimer kt_(ctx, "cqt_high", st);
     ma.span = kt_.span();
-    for (int rep = 0; rep < NC_PROBE_REPS(5); ++rep)
-      hipLaunchKernelGGL(cqt_mfma_kernel, dim3((unsigned)((1 + max_chunk_len / 512 + CH_FR - 1) / CH_FR), n),
-                         dim3(CM_NTH), cqm_lds_bytes(), st, ma);
+    hipLaunchKernelGGL(cqt_mfma_kernel, dim3((unsigned)((1 + max_chunk_len / 512 + CH_FR - 1) / CH_FR), n),
+                       dim3(CM_NTH), cqm_lds_bytes(), st, ma);
   }
   {
     MarkSpan ms_(ctx, "cqt_tail", st);

@@ -37,11 +37,7 @@ __device__ __forceinline__ float2 cmul_mi(float2 a) { return make_float2(a.y, -a
 // floored argument is a normal float, so log10f's denormal rescale (v_ldexp, two selects and the
 // subtract of its offset) is dropped; what stays is its own sequence, v_log_f32 and the product
 // with log10(2) compensated in f32 (ch + cl), and its non-finite select.  9 VALU against 14.
-#ifndef NC_DB_LIB_
-#define NC_DB_LIB_ 0  // A/B probe: the library log10f instead
-#endif
 __device__ __forceinline__ float db10_floor(float x) {
-  if (NC_DB_LIB_) return 10.0f * log10f(fmaxf(1e-10f, x));
   const float l = __builtin_amdgcn_logf(fmaxf(1e-10f, x));
   const float ch = __uint_as_float(0x3e9a209au), cl = __uint_as_float(0x3284fbcfu);
   const float ph = __fmul_rn(l, ch);

@@ -41,9 +41,6 @@ constexpr int SM_HALF = 528;  // float2 per half-size slot: 512 exchange element
 // waves at 96 VGPRs with a 120 KB reserve ran the step at 9.36-10.40 ms against 9.22-9.61 (16 waves,
 // 150 KB) and 16 waves with a 120 KB reserve at 9.31-9.72 (profiles/r5_stft_coresidency_ab.txt)
 constexpr size_t SM_LDS_RESERVE = 150 * 1024;
-#ifndef SM_NOEN_
-#define SM_NOEN_ 0  // timing probe: the frame energies left out even when asked for (outputs wrong)
-#endif
 // Round 6 (profiles/r6_stft_sync_*.txt): with a static interleave (wave w: frames
 // 16 G + w) the free-running waves of a workgroup drift apart by tens of frame groups, so the 4x
 // frame overlap is re-fetched from beyond the L2: reads 1.62x the algorithmic bytes.  Keeping them
@@ -482,7 +479,7 @@ int launch_stft_mel(Context& ctx, const StftMelArgs& args, hipStream_t st) {
   {
     KTimer kt_(ctx, "stft_mel", st);
     a.span = kt_.span();
-    const bool en = a.frame_energy != nullptr && !SM_NOEN_;
+    const bool en = a.frame_energy != nullptr;
     if (wide) {  // a context at another sample rate (nc_create_rate): tempo seams only
       if (a.hop == 512 && en)
         hipLaunchKernelGGL((stft_mel_kernel<true, true, kMelJ0w, kMelJ1w>), dim3(grid), dim3(SM_THREADS), lds, st, a);

@@ -3,8 +3,8 @@ results), checked against a model of the hardware rules they were designed for:
 
 * `xcd_remap` (nc_device.h) must be a permutation of the workgroup ids for every grid size,
   or workgroups would be skipped or run twice;
-* the fragment reads of `cqt_mfma_kernel` (image pads `cm_pad`, or since round 5 the XOR
-  swizzle `cm_phys` of hop-64 / hop-32 images, cqt.hip) and of
+* the fragment reads of `cqt_mfma_kernel` (the XOR swizzle `cm_phys` of hop-64 / hop-32
+  images, cqt.hip) and of
   `cqt_mfma_low_kernel` (image swizzle `c2_sw`, round 5) must be free of LDS bank conflicts under the
   `ds_read_b128` lane groups of MI355X_MICROARCH.md (LDS table): one LDS cycle per group.
 
@@ -45,25 +45,7 @@ def cm_hop(o):
     return 512 >> o
 
 
-def cm_pad(o):  # cqt.hip, the padded layout of CH_SWZ_=0 builds (the default until round 5)
-    return 16 if cm_hop(o) >= 32 else 0
-
-
-@pytest.mark.parametrize("octave", [3, 4, 5, 6])
-def test_octave_3_6_image_reads_conflict_free(octave):
-    """A fragment: row 16 rt + (lane & 15) of the image, k offset 8 (lane >> 4) halves, rows
-    hop + pad halves apart, a pad after every hop samples (cqt_mfma_kernel abase / kt)."""
-    hop, pad = cm_hop(octave), cm_pad(octave)
-    for rt in range(4):
-        for ks in range(32):
-            kt = 32 * ks + (32 * ks // hop) * pad
-            halves = [(16 * rt + (l & 15)) * (hop + pad) + 8 * (l >> 4) + ((8 * (l >> 4)) // hop) * pad + kt
-                      for l in range(64)]
-            assert all(h % 8 == 0 for h in halves)  # 16-byte aligned pieces
-            assert b128_cycles([h // 2 for h in halves]) == 4, (octave, rt, ks)
-
-
-# cqt.hip cm_swz_k / cm_swz_m / cm_phys (the default since round 5): piece P of a hop-64 or hop-32
+# cqt.hip cm_swz_k / cm_swz_m / cm_phys (the layout since round 5): piece P of a hop-64 or hop-32
 # image sits at P ^ h[(P >> 4) & m]; hop 16 and 8 are unpadded and unswizzled
 CM_SWZ = {64: (0xC638, 3), 32: (0xF8, 1)}
 

@@ -4,7 +4,7 @@
 # tools/traffic.py -> profiles/NAME (default r3_traffic.json).     usage: tools/pmc_traffic.sh OUTDIR [NAME]
 set -o pipefail
 OUT=$1
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 export TMPDIR=/tmp
 mkdir -p $R/$OUT
 for c in FETCH_SIZE WRITE_SIZE; do

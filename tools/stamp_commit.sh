@@ -1,6 +1,6 @@
 #!/bin/bash
 # Writes the current commit (plus "-dirty" when kernel sources differ from it) to .build_commit:
-# the tree gpurun sends to the GPU box has no .git, and bench.py / tools/traffic.py stamp their
+# a copy of the tree sent to a GPU machine has no .git, and bench.py / tools/traffic.py stamp their
 # outputs with it (bench.build_provenance).  Run before a GPU call.
 cd "$(dirname "$0")/.."
 c=$(git rev-parse --short HEAD)
